@@ -46,6 +46,7 @@ PEAK_HBM_GBS = 8000.0           # same guide: HBM3E peak (about 6.3 TB/s achieva
 PEAK_BF16_MFMA_TFLOPS = 2500.0  # same guide: dense bf16 MFMA (the split-bf16 mode issues six bf16 products per fp32 product)
 NOMINAL_GHZ = 2.4                 # MI355X peak engine clock (MI355X_MICROARCH.md): what the peak TFLOP/s figures are quoted at
 PEAK_FP32_VALU_TFLOPS = 157.3
+HEADLINE_SETTLE_STEPS = 200       # extra warm-up of the headline after --warmup: ~70 ms of steps, the time the chip takes to reach its sustained clock
 
 
 def parse():
@@ -53,7 +54,8 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=30)
-    ap.add_argument("--windows", type=int, default=5, help="timed windows of --steps steps each; the median window is reported")
+    ap.add_argument("--windows", type=int, default=1,
+                    help="split the --steps timed steps into this many consecutive windows; the median window's time per step is reported")
     ap.add_argument("--n", "--latent-dim", dest="n", type=int, default=10)
     ap.add_argument("--batch-size", type=int, default=6144)
     ap.add_argument("--p", type=int, default=2)
@@ -89,6 +91,9 @@ def parse():
                     help="only the multi-rank control flow (rendezvous, barrier-bracketed windows, max over ranks, one JSON line from rank 0) around a "
                          "stub step; works on CPU ranks over gloo.  Nothing is measured")
     ap.add_argument("--no-dropin", action="store_true", help="skip the drop-in leg (the reference's train_step on the swapped-in modules, N = 1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller -- the [loss, pos, neg] vector and every "
+                         "parameter and gradient of the encoder -- as DIR/<name>.npy (float32, rank 0)")
     return ap.parse_args()
 
 
@@ -648,16 +653,31 @@ def capture_or_eager(tr, args, rank, world, device):
     return use_graph
 
 
-def timed_windows(tr, steps, warmup, windows, world, device):
+def split_steps(total, windows):
+    """`total` timed steps as `windows` consecutive windows whose sizes differ by at most one (sum = `total`)."""
+    k = max(1, min(windows, total))
+    return [total // k + (1 if i < total % k else 0) for i in range(k)]
+
+
+def timed_windows(tr, steps, warmup, windows, world, device, settle=None):
     """`warmup` untimed steps (+ >= 60 ms of continuous work: the chip settles at its sustained clock only after tens of
-    milliseconds, see _graph_time), then `windows` windows of EXACTLY `steps` steps, every window bracketed by barrier +
-    synchronize on both sides and reduced with MAX over the ranks.  Returns (window seconds, extra warm-up steps)."""
+    milliseconds, see _graph_time), then `windows` windows of EXACTLY `steps` steps (or, with `steps` a list, one window per
+    entry of that many steps), every window bracketed by barrier + synchronize on both sides and reduced with MAX over the ranks.
+    `settle` replaces the 60 ms of extra warm-up on one rank by a FIXED step count (the headline: the same arguments then run the
+    same number of steps, so the last timed step sees the same inputs from run to run).
+    Returns (window seconds, extra warm-up steps)."""
     sync = torch.cuda.synchronize if device.type == "cuda" else (lambda: None)   # (--launch-check runs on CPU ranks too)
+    sizes = list(steps) if isinstance(steps, (list, tuple)) else [steps] * max(1, windows)
     for _ in range(warmup):
         tr.step()
     sync()
     extra_warm = 0
-    if world == 1:
+    if world == 1 and settle is not None:
+        for _ in range(settle):
+            tr.step()
+        extra_warm = settle
+        sync()
+    elif world == 1:
         t_w = time.perf_counter()
         while time.perf_counter() - t_w < 0.06:
             for _ in range(10):
@@ -669,12 +689,12 @@ def timed_windows(tr, steps, warmup, windows, world, device):
         for _ in range(extra_warm):
             tr.step()
     window_s = []
-    for _ in range(max(1, windows)):
+    for n_steps in sizes:
         if world > 1:
             dist.barrier()
         sync()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(n_steps):
             tr.step()
         sync()
         if world > 1:
@@ -686,6 +706,25 @@ def timed_windows(tr, steps, warmup, windows, world, device):
             el = float(t.item())
         window_s.append(el)
     return window_s, extra_warm
+
+
+def dump_outputs(tr, out_dir):
+    """What the last step handed its caller, as <out_dir>/<name>.npy in float32: `loss` (the [loss, pos, neg] vector ContrastiveTrainer.step
+    returns) and, for every parameter of the encoder f (updated in place by the step), `param.<name>` and `grad.<name>` (its .grad).
+    About 7 MB at the headline size."""
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": tr.loss_out[3 * tr.B:]}
+    for name, prm in tr.f.named_parameters():
+        arrays[f"param.{name}"] = prm.detach()
+        arrays[f"grad.{name}"] = prm.grad
+    total = 0
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(t.detach().float().cpu().numpy())
+        total += a.nbytes
+        if total > 64 << 20:
+            raise SystemExit(f"--dump-outputs: more than 64 MB at {name}")
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def comm_leg(tr, rank, world, device, reps=20):
@@ -1024,7 +1063,7 @@ def launch_check(args, rank, world, device):
                 dist.all_reduce(self.t)
                 self.t /= world
     stub = _Stub()
-    window_s, extra_warm = timed_windows(stub, args.steps, args.warmup, args.windows, world, device)
+    window_s, extra_warm = timed_windows(stub, split_steps(args.steps, args.windows), args.warmup, args.windows, world, device)
     seen = torch.tensor([1.0], device=device)
     if world > 1:
         dist.all_reduce(seen)
@@ -1079,10 +1118,13 @@ def main():
     tr = build_trainer(args, device, world)
     args._f16_headline = bool(getattr(tr, "split_f16", False))
     use_graph = capture_or_eager(tr, args, rank, world, device)
-    # "median of 5 windows" -- a short driver run (--steps 20 = ~11 ms of GPU time per window) is then not at the
-    # mercy of one scheduling hiccup
-    window_s, extra_warm = timed_windows(tr, args.steps, args.warmup, args.windows, world, device)
-    elapsed = float(np.median(window_s))
+    # EXACTLY --steps timed steps, split into --windows windows (the median window's time per step is reported), after a fixed
+    # number of settle steps: the same arguments always run the same steps (--dump-outputs compares the last one across builds)
+    sizes = split_steps(args.steps, args.windows)
+    window_s, extra_warm = timed_windows(tr, sizes, args.warmup, len(sizes), world, device, settle=HEADLINE_SETTLE_STEPS)
+    elapsed = float(np.median([w / k for w, k in zip(window_s, sizes)])) * args.steps     # seconds for --steps steps at the median rate
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tr, args.dump_outputs)
     last = tr.loss_out[3 * tr.B:].clone()
     loss_vals = [float(v) for v in last.cpu()]
     split = bool(tr.split_bf16)
@@ -1100,8 +1142,9 @@ def main():
                     % ("f16x2" if getattr(tr, "split_f16_wide", False) else "bf16x3"))
                    if wide_split else "f32")), "data": "synthetic",
         "global_steps_per_s": args.steps / elapsed,
-        "warmup_extra_steps": extra_warm, "windows": len(window_s), "timed_steps_total": args.steps * len(window_s), "timing": "median window of `windows` x `steps` steps",
-        "window_ms_per_step": [round(1e3 * w / args.steps, 4) for w in window_s],
+        "warmup_extra_steps": extra_warm, "windows": len(window_s), "timed_steps_total": sum(sizes),
+        "timing": "`steps` timed steps in `windows` consecutive windows; ms_per_step of the median window",
+        "window_ms_per_step": [round(1e3 * w / k, 4) for w, k in zip(window_s, sizes)],
         "config": {"workload": f"main_mlp.py --n {args.n} --n-mixing-layer 3 --p {args.p} --batch-size {args.batch_size} "
                                f"--space-type {args.space_type} (unsupervised step: sample->g->f->LpSimCLR->bwd->Adam; encoder {enc})",
                    "batch_per_gpu": args.batch_size, "global_batch": args.batch_size * world,

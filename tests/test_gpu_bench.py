@@ -57,3 +57,35 @@ def test_bench_gpus_2_starts_its_own_ranks_and_falls_back_to_eager():
     assert [e["rank"] for e in line["ranks"]] == [0, 1] and all(e["world_size_seen"] == 2 for e in line["ranks"])
     assert sum(1 for l in r.stdout.splitlines() if l.startswith("{")) == 1        # only rank 0 prints
     assert abs(line["final_loss"]) < 20
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR`: after exactly `--steps` timed steps the last step's results (loss vector, parameters and gradients of the
+    encoder) land in DIR as float32 .npy files, at most 64 MB.  Two runs with the same arguments except the split into windows run the
+    same steps on the same inputs: a different step count would change the batch, and with it the gradients by far more than the
+    bound below."""
+    import numpy as np
+    runs = []
+    for windows in ("1", "3"):
+        d = tmp_path / f"w{windows}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "12", "--warmup", "3", "--windows", windows,
+                            "--no-cpu-baseline", "--no-roofline", "--no-dropin", "--no-native-leg", "--no-dry-leg", "--no-secondary",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 12 and line["timed_steps_total"] == 12 and line["windows"] == int(windows)
+        assert line["ms_per_step"] > 0 and abs(line["value"] * line["ms_per_step"] - 1e3) < 1e-6 * line["value"] * line["ms_per_step"]
+        files = sorted(p.name for p in d.iterdir())
+        out = {f[:-4]: np.load(d / f) for f in files}
+        assert sum((d / f).stat().st_size for f in files) <= 64 << 20
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in out.values())
+        assert out["loss"].tolist() == [line["final_loss"], line["final_pos"], line["final_neg"]]
+        n_lin = 7      # get_mlp(10, 10, [100, 500, 500, 500, 500, 100]): seven Linear layers, weight + bias each
+        assert sum(1 for k in out if k.startswith("param.")) == sum(1 for k in out if k.startswith("grad.")) == 2 * n_lin
+        assert out["param.0.weight"].shape == out["grad.0.weight"].shape == (100, 10)
+        runs.append(out)
+    a, b = runs
+    assert sorted(a) == sorted(b)
+    for k in a:
+        den = max(float(np.abs(a[k]).max()), 1e-30)
+        assert float(np.abs(a[k] - b[k]).max()) / den < 1e-3, k

@@ -181,8 +181,10 @@ def test_grad_bucket_partition():
 
 def _host_moment_stand_ins(monkeypatch):
     """The two device entry points disentanglement_utils calls, stood in for by host arithmetic so that ITS host logic (every score as a
-    function of the moment matrix) is tested without a GPU; the kernels themselves are tested with -m gpu."""
+    function of the moment matrix) is tested without a GPU; the kernels themselves are tested with -m gpu.  The data stays on the host
+    on a machine with a GPU as well (the module sends host tensors to the GPU when there is one)."""
     from cl_ica_amd import ops
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
 
     def moments(a, b=None):
         cols = [a.double()] + ([b.double()] if b is not None else []) + [torch.ones(a.shape[0], 1, dtype=torch.float64)]
@@ -288,48 +290,37 @@ def test_train_mlp_cli_surface():
     assert (s.space, s.conditional, s.marginal, s.c_p) == ("real", "gennorm", "normal", 3.0)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="needs the reference checkout (build container only)")
 def test_n3_our_checkpoints_load_into_the_reference():
     """The reverse direction of tests/test_gpu_next_rows.py::test_n3_*: state dicts saved from cl_ica_amd's get_mlp /
-    MixingMLP / BetaVAE_H load into the REFERENCE's modules with strict key matching (same keys, shapes, values)."""
-    import subprocess, sys, tempfile, textwrap
-    code = textwrap.dedent('''
-        import sys, io, contextlib, warnings
-        warnings.filterwarnings("ignore")
-        import numpy as np, torch
-        sys.path.insert(0, "%s")
-        from cl_ica_amd import encoders as E, invertible_network_utils as I
-        from cl_ica_amd.kitti_masks.model import BetaVAE_H as K
-        ours = {}
-        for head in (None, "learnable_sphere", "learnable_box", "fixed_sphere", "fixed_box"):
-            ours["f_%%s" %% head] = E.get_mlp(4, 4, [12, 20, 12], output_normalization=head).state_dict()
+    MixingMLP / BetaVAE_H load into the REFERENCE's modules with strict key matching.  The reference's side is its state-dict
+    layout, stored in tests/golden/g26_state_dict_layout.json (tests/golden/gen_goldens_layout.py): strict loading accepts a
+    state dict exactly when it has the same keys, and copying keeps the values exactly when shapes and dtypes agree too --
+    so ours, after a torch.save / torch.load round trip, must match that layout entry for entry, in order."""
+    import json, tempfile
+    from cl_ica_amd import encoders as E, invertible_network_utils as I
+    from cl_ica_amd.kitti_masks.model import BetaVAE_H as K
+    with open(os.path.join(ROOT_DIR, "tests", "golden", "g26_state_dict_layout.json")) as fh:
+        ref = json.load(fh)
+    ours = {}
+    for head in (None, "learnable_sphere", "learnable_box", "fixed_sphere", "fixed_box"):
+        ours["f_%s" % head] = E.get_mlp(4, 4, [12, 20, 12], output_normalization=head).state_dict()
+    rng_state = np.random.get_state()
+    try:
         np.random.seed(1)
         with contextlib.redirect_stdout(io.StringIO()):
             ours["g"] = I.construct_invertible_mlp(n=4, n_layers=3, cond_thresh_ratio=0.0, n_iter_cond_thresh=50).state_dict()
-        ours["kitti"] = K(z_dim=5, nc=1, box_norm=True).state_dict()
-        torch.save(ours, sys.argv[1])
-        for m in [k for k in sys.modules if k.split(".")[0] == "cl_ica_amd"]:
-            del sys.modules[m]
-        sys.path.insert(0, "/root/reference")
-        import encoders as RE, invertible_network_utils as RI
-        from kitti_masks.model import BetaVAE_H as RK
-        ours = torch.load(sys.argv[1])
-        for head in (None, "learnable_sphere", "learnable_box", "fixed_sphere", "fixed_box"):
-            r = RE.get_mlp(4, 4, [12, 20, 12], output_normalization=head)
-            res = r.load_state_dict(ours["f_%%s" %% head], strict=True)
-            assert not res.missing_keys and not res.unexpected_keys
-            for k, v in r.state_dict().items():
-                assert torch.equal(v, ours["f_%%s" %% head][k])
-        with contextlib.redirect_stdout(io.StringIO()):
-            rg = RI.construct_invertible_mlp(n=4, n_layers=3, cond_thresh_ratio=0.0, n_iter_cond_thresh=50)
-        rg.load_state_dict(ours["g"], strict=True)
-        RK(z_dim=5, nc=1, box_norm=True).load_state_dict(ours["kitti"], strict=True)
-        print("ok")
-    ''') % ROOT_DIR
+    finally:
+        np.random.set_state(rng_state)
+    ours["kitti"] = K(z_dim=5, nc=1, box_norm=True).state_dict()
     with tempfile.TemporaryDirectory() as d:
-        r = subprocess.run([sys.executable, "-c", code, os.path.join(d, "ours.pth")], capture_output=True, text=True,
-                           env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stderr[-2000:]
+        torch.save(ours, os.path.join(d, "ours.pth"))
+        loaded = torch.load(os.path.join(d, "ours.pth"))
+    assert sorted(loaded) == sorted(ref)
+    for name, layout in ref.items():
+        got = [[k, list(v.shape), str(v.dtype).replace("torch.", "")] for k, v in loaded[name].items()]
+        assert got == layout, (name, got, layout)
+        for k, v in loaded[name].items():
+            assert torch.equal(v, ours[name][k]), (name, k)
 
 
 def test_lazy_stacking_mechanics_on_cpu():

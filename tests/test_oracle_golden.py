@@ -267,7 +267,14 @@ def test_torch_port_goldens(golden):
         mean, per, (pm, nm) = T.lp_simclr_loss(a, b, cc, p=int(m["p"]), tau=float(m["tau"]), alpha=float(m["alpha"]),
                                                compat=bool(m["compat"]), pow=bool(m["pow"]))
         mean.backward()
-        assert np.array_equal(per.detach().numpy(), c["out"]["loss_i"]) or rel_err(per.detach().numpy(), c["out"]["loss_i"]) < 1e-6
+        # the loss rows' rounding scale as in _check_loss_case (cancelling summands, and lse_i = log of a sum over B3 rows - log B3):
+        # torch's CPU kernels round these rows differently on different host CPUs -- the goldens match bit for bit on the one that
+        # wrote them, and within a few ulps of that scale elsewhere (ATEN_CPU_CAPABILITY=default shows it on any machine)
+        orc = O.lp_simclr_loss(c["in"]["z1"], c["in"]["z2"], c["in"]["z3"], p=float(m["p"]), tau=float(m["tau"]), alpha=float(m["alpha"]),
+                               compat=bool(m["compat"]), pow=bool(m["pow"]), grad=False)
+        got, ref = per.detach().numpy(), c["out"]["loss_i"]
+        comp = max(float(np.abs(ref).max()), float(np.abs(orc["lse"]).max()) + np.log(c["in"]["z3"].shape[0] + 1.0))
+        assert np.array_equal(got, ref) or float(np.abs(got.astype(np.float64) - ref).max()) / comp < 1e-6
         assert rel_err(a.grad.numpy(), c["out"]["dz1"]) < 1e-5
         n += 1
     assert n > 50
