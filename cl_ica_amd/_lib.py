@@ -7,7 +7,8 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, Optional, Tuple
+import weakref
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -309,6 +310,35 @@ def workspace(tag: str, nbytes: int, device: torch.device) -> torch.Tensor:
     key = (device.index if device.index is not None else torch.cuda.current_device(), stream_ptr(), tag)
     buf = _WS.get(key)
     if buf is None or buf.numel() < nbytes:
+        # (a buffer a captured graph holds stays alive through the graph's reference: growing only replaces the cache's)
         buf = torch.zeros(max(nbytes, 1024), dtype=torch.uint8, device=device)
         _WS[key] = buf
+    note_graph_use(buf)
     return buf
+
+
+# ---- buffers owned by captured graphs (cl_ica_amd.graphed) --------------------------------------------------------------------------
+# A graph replays raw pointers: every cache-held buffer its recorded step reads or writes must outlive it and must not be handed to
+# another owner (another encoder's weights packed into it, another step's scratch).  While `capture_train_step` records, every cache
+# that hands a buffer to a launch reports it here (`note_graph_use`); the replaying callable then keeps those tensors (`pin`), and
+# the caches ask `pinned` before they reuse a buffer for somebody else.
+_CAPTURE_NOTES: Optional[List[torch.Tensor]] = None
+_PINS: Dict[int, "weakref.WeakSet"] = {}      # data_ptr -> the live owners (replay callables) that hold a tensor starting there
+
+
+def note_graph_use(*ts) -> None:
+    if _CAPTURE_NOTES is not None and torch.cuda.is_current_stream_capturing():
+        _CAPTURE_NOTES.extend(t for t in ts if t is not None)
+
+
+def pin(owner, tensors) -> None:
+    """`owner` (weak-referenceable, holds `tensors` itself) now owns `tensors`: `pinned` answers True for them while it lives."""
+    for p in [p for p, s in _PINS.items() if not s]:
+        del _PINS[p]
+    for t in tensors:
+        _PINS.setdefault(t.data_ptr(), weakref.WeakSet()).add(owner)
+
+
+def pinned(t: Optional[torch.Tensor]) -> bool:
+    """Is `t` (its storage's start) held by a live captured graph?"""
+    return t is not None and bool(_PINS.get(t.data_ptr()))

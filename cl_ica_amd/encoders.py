@@ -16,6 +16,7 @@ import weakref
 import torch
 from torch import nn
 
+from . import _lib
 from . import layers as ls
 from . import lazy
 from . import ops
@@ -77,8 +78,9 @@ class _MLPFusedFn(torch.autograd.Function):
         ws = _MLPFusedFn._ws_cache.get(key)
         if ws is None:
             if len(_MLPFusedFn._ws_cache) >= 4:      # each entry is 30-60 MB: a few shapes (train / eval batch), not a leak
-                _MLPFusedFn._ws_cache.clear()
+                _evict_unpinned(_MLPFusedFn._ws_cache)
             ws = _MLPFusedFn._ws_cache[key] = ops.mlp_wgrad_workspace(M, shapes, dev)
+        _lib.note_graph_use(ws)
         return ws
 
     @staticmethod
@@ -93,11 +95,15 @@ class _MLPFusedFn(torch.autograd.Function):
         dev = params_w[0].device
         c = _MLPFusedFn._pack_cache.get(dev)
         if c is not None and c["key"] == key:
+            _lib.note_graph_use(c["packed"], c["packed_t"])
             return c["packed"], c["packed_t"], key
         shapes = [tuple(w.shape) for w in params_w]
-        reuse = c is not None and c["shapes"] == shapes
+        # (buffers a captured graph owns are re-packed in place only with the weights that graph packs into them: another encoder's
+        #  call gets buffers of its own, or the graph's next replay would run on that encoder's weights -- and that encoder on the graph's)
+        reuse = c is not None and c["shapes"] == shapes and (_weight_ptrs(key) == _weight_ptrs(c["key"]) or not _lib.pinned(c["packed"]))
         packed, packed_t = ops.mlp_pack_both([w.detach() for w in params_w], c["packed"] if reuse else None, c["packed_t"] if reuse else None)
         _MLPFusedFn._pack_cache[dev] = dict(key=key, shapes=shapes, packed=packed, packed_t=packed_t)
+        _lib.note_graph_use(packed, packed_t)
         return packed, packed_t, key
 
     @staticmethod
@@ -159,6 +165,17 @@ class _MLPFusedFn(torch.autograd.Function):
         return (dx, None, *grads)
 
 
+def _weight_ptrs(key):
+    """The weights' data pointers in a pack key (`_MLPFusedFn._weights_key`): which encoder a pack entry belongs to."""
+    return tuple(k[0] for k in key[1:])
+
+
+def _evict_unpinned(cache) -> None:
+    """Make room in a workspace cache: every entry goes except those a captured graph owns (it replays their pointers)."""
+    for k in [k for k, v in cache.items() if not _lib.pinned(v)]:
+        del cache[k]
+
+
 def _adjacent_rows(gs, rows, n):
     """The tensors `gs` ([rows[i], n] each) as ONE [sum(rows), n] tensor if they already lie behind one another in one storage
     (contiguous fp32 row blocks), else None."""
@@ -197,7 +214,6 @@ class _SplitPlan:
 
     def __init__(self, dev, M, shapes, f16=False):
         import ctypes as C
-        from . import _lib
         lib = _lib.load()
         L = len(shapes)
         self.dev, self.M, self.L, self.shapes, self.f16 = dev, M, L, shapes, f16
@@ -254,12 +270,16 @@ class _MLPFusedSplitFn(torch.autograd.Function):
     grouped weight gradients, with hidden activations / dZ handed from kernel to kernel as bf16 planes where a matrix-core weight
     gradient is their only reader.  ``CLICA_SPLIT_BF16=0`` / ``CLICA_DROPIN_SPLIT=0`` keep the fp32-MFMA kernels.
 
-    ``apply(slope, n_in, x_0 .. x_{n_in-1}, W_0, b_0, ...)``: the `n_in` row batches run STACKED through one launch per phase and
-    come back as `n_in` outputs (row slices of one result) -- what `lazy.defer` does with the reference's two encoder calls per
-    step, without CatBackward / SliceBackward nodes around the function (their backward was five small launches)."""
+    ``apply(slope, n_in, training, x_0 .. x_{n_in-1}, W_0, b_0, ...)``: the `n_in` row batches run STACKED through one launch per phase
+    and come back as `n_in` outputs (row slices of one result) -- what `lazy.defer` does with the reference's two encoder calls per
+    step, without CatBackward / SliceBackward nodes around the function (their backward was five small launches).  `training`: the
+    caller's grad mode (inside `forward` it is always off).  A forward outside a training step (evaluation under ``no_grad`` /
+    ``inference_mode``) of an f16x2 encoder runs in bf16x3 on a weight pack of its own: it must not record maxima into, or raise the
+    guard of, the state the next training step's scales and verdict come from, and its inputs may lie far beyond those scales."""
 
     _pack_cache = {}
     _ws_cache = {}
+    _graph_packs = {}     # (device, weight pointers) -> a pack entry a captured graph owns, while it is not the device's current entry
 
     @staticmethod
     def _packed(params_w, key=None, s16=None, force=False):
@@ -268,12 +288,21 @@ class _MLPFusedSplitFn(torch.autograd.Function):
             key = _MLPFusedFn._weights_key(params_w)
         dev = params_w[0].device
         c = _MLPFusedSplitFn._pack_cache.get(dev)
-        if c is not None and c["key"] == key and c["s16"] is s16 and not force:
-            return c["packed"], c["packed_t"], key
         ptrs = tuple(k[0] for k in key[1:])
+        if c is None or c.get("ptrs") != ptrs or c["s16"] is not s16:
+            # A captured graph reads its pack at the start of every replay and re-packs it only at its own step end: eager calls of its
+            # encoder (a batch of another shape, evaluation, steps between replays) must work on -- and leave up to date -- THAT pack
+            g = _MLPFusedSplitFn._graph_packs.get((dev, ptrs))
+            if g is not None and g["s16"] is s16 and _lib.pinned(g["packed"]):
+                del _MLPFusedSplitFn._graph_packs[(dev, ptrs)]
+                if c is not None and _lib.pinned(c["packed"]):
+                    _MLPFusedSplitFn._graph_packs[(dev, c.get("ptrs"))] = c
+                c = _MLPFusedSplitFn._pack_cache[dev] = g
+        if c is not None and c["key"] == key and c["s16"] is s16 and not force:
+            _lib.note_graph_use(c["packed"], c["packed_t"])
+            return c["packed"], c["packed_t"], key
         if c is not None and c.get("ptrs") == ptrs and c["strides"] == [w.stride() for w in params_w] and c["s16"] is s16:
             # the same parameter tensors with new values (every training step): the argument arrays of the first call still hold
-            from . import _lib
             if s16 is None:
                 _lib.check(_lib.load().clica_mlp_pack_split_both(*c["args"], c["packed"].data_ptr(), c["packed_t"].data_ptr(), _lib.stream_ptr()),
                            "clica_mlp_pack_split_both")
@@ -281,10 +310,12 @@ class _MLPFusedSplitFn(torch.autograd.Function):
                 _lib.check(_lib.load().clica_mlp_pack_split16_both(*c["args"], c["packed"].data_ptr(), c["packed_t"].data_ptr(),
                                                                    s16.state.buf.data_ptr(), _lib.stream_ptr()), "clica_mlp_pack_split16_both")
             c["key"] = key
+            _lib.note_graph_use(c["packed"], c["packed_t"])
             return c["packed"], c["packed_t"], key
         import ctypes as C
         shapes = [tuple(w.shape) for w in params_w]
-        reuse = c is not None and c["shapes"] == shapes and c["s16"] is s16
+        # (another encoder's weights never go into buffers a captured graph owns: see _MLPFusedFn._packed)
+        reuse = c is not None and c["shapes"] == shapes and c["s16"] is s16 and (c.get("ptrs") == ptrs or not _lib.pinned(c["packed"]))
         ws = [w.detach() for w in params_w]
         packed, packed_t = ops.mlp_pack_split_both(ws, c["packed"] if reuse else None, c["packed_t"] if reuse else None,
                                                    state=None if s16 is None else s16.state)
@@ -293,9 +324,15 @@ class _MLPFusedSplitFn(torch.autograd.Function):
         if all(w.dim() == 2 and w.stride(1) == 1 and w.is_cuda and w.dtype == torch.float32 for w in ws):
             args = (L, (C.c_void_p * L)(*[w.data_ptr() for w in ws]), (C.c_int64 * L)(*[w.stride(0) for w in ws]),
                     (C.c_int32 * L)(*[s_[0] for s_ in shapes]), (C.c_int32 * L)(*[s_[1] for s_ in shapes]))
+        if c is not None and not reuse and _lib.pinned(c["packed"]):
+            gp = _MLPFusedSplitFn._graph_packs
+            for k in [k for k, e in gp.items() if not _lib.pinned(e["packed"])]:
+                del gp[k]
+            gp[(dev, c.get("ptrs"))] = c
         _MLPFusedSplitFn._pack_cache[dev] = dict(key=key, shapes=shapes, packed=packed, packed_t=packed_t, s16=s16,
                                                  params=[weakref.ref(w) for w in params_w], args=args,
                                                  ptrs=ptrs if args is not None else None, strides=[w.stride() for w in params_w])
+        _lib.note_graph_use(packed, packed_t)
         return packed, packed_t, key
 
     @staticmethod
@@ -312,18 +349,17 @@ class _MLPFusedSplitFn(torch.autograd.Function):
 
     @staticmethod
     def _wgrad_ws(dev, M, shapes):
-        from . import _lib
         key = (dev, _lib.stream_ptr(), M, tuple(shapes))
         ws = _MLPFusedSplitFn._ws_cache.get(key)
         if ws is None:
             if len(_MLPFusedSplitFn._ws_cache) >= 4:
-                _MLPFusedSplitFn._ws_cache.clear()
+                _evict_unpinned(_MLPFusedSplitFn._ws_cache)
             ws = _MLPFusedSplitFn._ws_cache[key] = ops.mlp_wgrad_split_workspace(M, shapes, dev)
+        _lib.note_graph_use(ws)
         return ws
 
     @staticmethod
-    def forward(ctx, slope, n_in, *args):
-        from . import _lib
+    def forward(ctx, slope, n_in, training, *args):
         xs, params = args[:n_in], args[n_in:]
         L = len(params) // 2
         x = xs[0].detach() if n_in == 1 else torch.cat([t.detach() for t in xs], 0)
@@ -331,8 +367,12 @@ class _MLPFusedSplitFn(torch.autograd.Function):
         M, dev = x.shape[0], x.device
         pw = params[0::2]
         s16 = _s16_ctx(params, slope)            # f16x2 (the engine's default arithmetic) when the flat Adam owns these parameters, else bf16x3
-        calibrate = s16 is not None and s16.begin_forward(pw)
-        packed, _, key = _MLPFusedSplitFn._packed(pw, s16=s16, force=calibrate)
+        if s16 is not None and not training:
+            s16, key = None, None
+            packed = ops.mlp_pack_split_both([w.detach() for w in pw])[0]      # (one pack launch per evaluation call; the cache stays the step's)
+        else:
+            calibrate = s16 is not None and s16.begin_forward(pw)
+            packed, _, key = _MLPFusedSplitFn._packed(pw, s16=s16, force=calibrate)
         pl = _SplitPlan.get(dev, M, tuple(tuple(w.shape) for w in pw), s16 is not None)
         arena = torch.empty(pl.f_bytes, dtype=torch.uint8, device=dev)
         y = torch.empty((M, pl.shapes[-1][0]), dtype=torch.float32, device=dev)
@@ -345,6 +385,7 @@ class _MLPFusedSplitFn(torch.autograd.Function):
         if s16 is None:
             _lib.check(_lib.load().clica_mlp_fwd_split(*fargs, _lib.stream_ptr()), "clica_mlp_fwd_split")
         else:
+            _lib.note_graph_use(s16.state.buf)
             st_ptr = s16.state.buf.data_ptr()
             if calibrate:
                 # scales not measured on these parameters yet: this pass (weights packed and activations cut on the scales in force)
@@ -360,7 +401,8 @@ class _MLPFusedSplitFn(torch.autograd.Function):
         ctx.pack_key = key
         ctx.params = params
         ctx.set_materialize_grads(False)
-        ctx.save_for_backward(x, arena, *[w.detach() for w in pw])
+        if training:
+            ctx.save_for_backward(x, arena, *[w.detach() for w in pw])
         if n_in == 1:
             return y
         # the row blocks as tensors of their own on y's storage (not autograd views of y: a view output of a multi-output function
@@ -373,7 +415,6 @@ class _MLPFusedSplitFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *gys):
-        from . import _lib
         import ctypes as C
         L, slope, pl = ctx.L, ctx.slope, ctx.plan
         kinds, shapes, M, dev = pl.kinds, pl.shapes, pl.M, pl.dev
@@ -382,17 +423,17 @@ class _MLPFusedSplitFn(torch.autograd.Function):
         if ctx.n_in == 1:
             gy = gys[0]
             if gy is None:
-                return (None,) * (3 + 2 * L)
+                return (None,) * (4 + 2 * L)
             gy = gy.contiguous()
         else:
             if all(g is None for g in gys):
-                return (None,) * (2 + ctx.n_in + 2 * L)
+                return (None,) * (3 + ctx.n_in + 2 * L)
             gy = _adjacent_rows(gys, ctx.rows, shapes[-1][0])      # (the symmetric loss backward writes dz1 / dz2 into one buffer)
             if gy is None:
                 gy = torch.cat([g if g is not None else x.new_zeros((r, shapes[-1][0])) for g, r in zip(gys, ctx.rows)], 0)
         _lib.require_cuda(gy, "grad_output")
         need = ctx.needs_input_grad
-        need_x = any(need[2:2 + ctx.n_in])
+        need_x = any(need[3:3 + ctx.n_in])
         s16 = ctx.s16
         st = None if s16 is None else s16.state
         cur = _MLPFusedSplitFn._pack_cache.get(dev)
@@ -460,7 +501,7 @@ class _MLPFusedSplitFn(torch.autograd.Function):
                 dzf[l], lddz[l] = (gy.data_ptr(), gy.stride(0)) if l == L - 1 else (f32_ptr[l], shapes[l][0])
                 xf[l], ldxf[l] = (x.data_ptr(), x.stride(0)) if l == 0 else (fb + pl.f_outs[l - 1], shapes[l - 1][0])
         prm = ctx.params
-        in_place = _inplace_ok(prm, (True, True) + tuple(need[2 + ctx.n_in:]))
+        in_place = _inplace_ok(prm, (True, True) + tuple(need[3 + ctx.n_in:]))
         if in_place:
             dWs, dbs, acc = [prm[2 * l].grad for l in range(L)], [prm[2 * l + 1].grad for l in range(L)], 1
         else:
@@ -482,18 +523,18 @@ class _MLPFusedSplitFn(torch.autograd.Function):
         grads = [None] * (2 * L)
         if not in_place:
             for l in range(L):
-                grads[2 * l] = dWs[l] if need[2 + ctx.n_in + 2 * l] else None
-                grads[2 * l + 1] = dbs[l] if need[3 + ctx.n_in + 2 * l] else None
+                grads[2 * l] = dWs[l] if need[3 + ctx.n_in + 2 * l] else None
+                grads[2 * l + 1] = dbs[l] if need[4 + ctx.n_in + 2 * l] else None
         dxs = [None] * ctx.n_in
         if need_x:
             d0 = gy if L == 1 else (dz0 if dz0 is not None else torch.as_strided(barena.view(torch.float32), (M, shapes[0][0]), (shapes[0][0], 1), pl.b_f32[0] // 4))
             dx = ops.linear_dgrad(d0, ws[0], None, slope)
             off = 0
             for i, r in enumerate(ctx.rows):
-                dxs[i] = dx[off:off + r] if need[2 + i] else None
+                dxs[i] = dx[off:off + r] if need[3 + i] else None
                 off += r
         del keep
-        return (None, None, *dxs, *grads)
+        return (None, None, None, *dxs, *grads)
 
 
 S16_ENABLED = True           # test hook: False keeps the drop-in encoder on the bf16x3 arithmetic (as CLICA_SPLIT_ARITH=bf16 does)
@@ -553,8 +594,10 @@ def _s16_ctx(params, slope):
 
 
 def arith_state(module) -> dict:
-    """Which arithmetic the whole-encoder kernels of a drop-in encoder run in and, for f16x2, the state of its scales and of the guard
-    (host read + sync: log points, tests): flags (bit 0 overflow seen, bit 1 a step was withheld), `skipped` = steps withheld so far."""
+    """Which arithmetic the whole-encoder kernels of a drop-in encoder run in ("fp32", "bf16x3" or "f16x2") and, for f16x2, the state of its
+    scales and of the guard (host read + sync: log points, tests): flags (bit 0 overflow seen, bit 1 a step was withheld), `skipped` = steps withheld so far."""
+    if hasattr(module, "_structure") and not _dropin_split(module._structure()[6]):
+        return dict(arith="fp32")        # the whole-encoder kernels in native fp32 MFMA (CLICA_SPLIT_BF16=0, or widths beyond mlp_split_k's)
     lin = [m for m in module if isinstance(m, nn.Linear)]
     c = lin[0].weight.__dict__.get("_clica_s16") if lin else None
     if c is None:
@@ -663,7 +706,8 @@ class FusedMLP(nn.Sequential):
 
         def compute(xx):
             if _use_fused(fusable, xx.shape[0]):
-                y = _MLPFusedSplitFn.apply(slope, 1, xx, *params) if _dropin_split(split) else _MLPFusedFn.apply(xx, slope, *params)
+                y = (_MLPFusedSplitFn.apply(slope, 1, torch.is_grad_enabled(), xx, *params) if _dropin_split(split) else
+                     _MLPFusedFn.apply(xx, slope, *params))
             else:
                 y = _MLPStackFn.apply(xx, slope, *params)
             for m in post:
@@ -673,7 +717,7 @@ class FusedMLP(nn.Sequential):
         def compute_many(xlist):       # several pending calls as ONE function with several outputs (None: not on this path)
             if post or not (_use_fused(fusable, sum(t.shape[0] for t in xlist)) and _dropin_split(split)):
                 return None
-            return list(_MLPFusedSplitFn.apply(slope, len(xlist), *xlist, *params))
+            return list(_MLPFusedSplitFn.apply(slope, len(xlist), torch.is_grad_enabled(), *xlist, *params))
         # The reference's train_step calls the encoder twice per step (main_mlp.py:270-271).  A training call that does not fill the
         # chip on its own (fewer than 256 panels of 48 rows) is DEFERRED: if the same module is called again before anything uses the
         # result, both batches run as one stacked launch per phase (cl_ica_amd/lazy.py); any other use computes it right away.

@@ -21,6 +21,9 @@ What makes the unchanged closure capturable:
     other origin are gathered at the end of the graph and cost one stream synchronisation per step.
   * everything else the step does on the device already goes through stream-ordered launches on preallocated or graph-pool memory: the
     deferred stacking of the two encoder calls, the roll detection of the loss, the optimizer hooks that re-pack the weights at step end.
+    The buffers of the package's caches that the recorded launches use (fragment-order weight packs, weight-gradient slabs, loss
+    workspaces, the f16x2 state) are OWNED by the returned callable (``replay.owned``): the caches never free them or give them to
+    another encoder while it lives, so eager work of other encoders, other batch shapes and evaluation calls between replays is safe.
   * the optimizer must be capturable: ``cl_ica_amd.optim.Adam`` (device-side step counter) or ``torch.optim.Adam(..., capturable=True)``.
 Limits: tensor SHAPES are fixed at capture (a ragged last batch: call the original closure); host-side control flow inside the closure is
 frozen as recorded; ``.item()`` is the only host read the recorder understands (``float(t)``, ``t.cpu()``, ``print(t)`` inside the closure
@@ -165,7 +168,9 @@ def capture_train_step(train_step: Callable, data, *args, warmup: int = 3, **kwa
         raise RuntimeError("capture_train_step: another capture is in progress")
     graph = torch.cuda.CUDAGraph()
     slots: List[torch.Tensor] = []
+    from . import _lib
     rec = _RECORDER = _Recorder(device)
+    notes = _lib._CAPTURE_NOTES = []          # the cache-held buffers the recorded launches use (weight packs, slabs, workspaces, f16x2 state)
     try:
         # (the recorded call sees the batch as RollDeferring views of the static buffers: a torch.roll(z1, 1, 0) nobody reads -- the
         #  reference's z3, main_mlp.py:266 -- then records no launch; anything that does read it gets the rolled tensor)
@@ -179,6 +184,7 @@ def capture_train_step(train_step: Callable, data, *args, warmup: int = 3, **kwa
                     dev_buf = torch.stack([s.to(stacked_dtype) for s in slots])
     finally:
         _RECORDER = None
+        _lib._CAPTURE_NOTES = None
     if slots:
         host = torch.empty(len(slots), dtype=stacked_dtype, pin_memory=True)
     replays = [0]
@@ -209,6 +215,11 @@ def capture_train_step(train_step: Callable, data, *args, warmup: int = 3, **kwa
             return v
         return _tree_map(fill, recorded)
 
+    # the graph replays raw pointers into those buffers: it owns them from now on -- a cache may drop or replace its own reference
+    # (another encoder's call, more batch shapes than it keeps, a grown workspace) but never frees them or hands them to another owner
+    owned = list({id(t): t for t in notes}.values())
+    _lib.pin(replay, owned)
+    replay.owned = owned
     replay.graph = graph
     replay.static_inputs = static
     replay.n_host_scalars = len(slots) + sum(p.n for p in rec.publishers)

@@ -35,6 +35,10 @@ _META_GETTERS = {"shape", "dtype", "device", "requires_grad", "ndim", "layout", 
 _META_METHODS = {"dim", "size", "__len__", "ndimension", "numel", "nelement", "is_floating_point", "is_complex", "get_device",
                  "element_size", "is_contiguous_placeholder"}
 _ALL_PENDING = weakref.WeakSet()
+_PENDING_ROLLS = {}       # id -> weak reference of every LazyRoll not materialised yet (an in-place write to its source materialises it first;
+                          # not a WeakSet: tensors compare elementwise)
+_INPLACE_DUNDERS = {"__iadd__", "__isub__", "__imul__", "__itruediv__", "__ifloordiv__", "__imod__", "__ipow__", "__iand__", "__ior__",
+                    "__ixor__", "__ilshift__", "__irshift__", "__imatmul__", "__setitem__"}
 
 
 def enabled() -> bool:
@@ -142,6 +146,8 @@ class LazyOut(torch.Tensor):
             with torch._C.DisableTorchFunctionSubclass():      # metadata lives on the wrapper itself: no need to compute anything
                 return func(*args, **kwargs)
 
+        if _PENDING_ROLLS and _writes(name, kwargs):
+            _materialize_rolls_of(args, kwargs)
         if name == "roll" and args and type(args[0]) is LazyOut:
             # z3_rec = torch.roll(z1_rec, 1, 0) (main_mlp.py:272): LpSimCLRLoss never reads the rolled copy (losses.py: _PairLossSymFn), so the
             # roll itself is deferred as well -- any other consumer gets the real tensor through LazyRoll.materialize()
@@ -161,18 +167,30 @@ class LazyOut(torch.Tensor):
 class LazyRoll(torch.Tensor):
     """``torch.roll(source, shift, 0)`` of a deferred module output, itself deferred: the reference's ``z3_rec`` (main_mlp.py:272).
     ``LpSimCLRLoss`` recognises it by ``source`` and never computes it; every other consumer (any torch function, ``plain``) gets the
-    real rolled tensor, computed once with ordinary autograd."""
+    real rolled tensor, computed once with ordinary autograd.
+
+    The value is the roll of the source AS IT WAS at the ``torch.roll`` call, as with torch.roll itself: an in-place write that reaches
+    the source through its own ``__torch_function__`` (``z.add_(1)``, ``z += 1``, ``z[0] = 0``, ``out=z`` on a LazyOut or a
+    RollDeferring) materialises the pending roll first.  A write that bypasses the subclass (through a plain alias of the storage)
+    cannot be seen in time; it moves the source's version counter, and reading the roll then raises instead of returning the roll of
+    the new values."""
 
     @staticmethod
     def __new__(cls, source, shift: int):
         r = torch.Tensor._make_wrapper_subclass(cls, tuple(source.shape), dtype=source.dtype, device=source.device,
                                                 requires_grad=source.requires_grad)
         r.source, r.shift, r._value = source, int(shift), None
+        r._src_version = None if isinstance(source, LazyOut) else _version_of(source)    # (a LazyOut has no values yet: see LazyOut.__torch_function__)
+        _PENDING_ROLLS[id(r)] = weakref.ref(r, lambda _, k=id(r): _PENDING_ROLLS.pop(k, None))
         return r
 
     def materialize(self) -> torch.Tensor:
         if self._value is None:
+            if self._src_version is not None and self.source._version != self._src_version:
+                raise RuntimeError("cl_ica_amd: the source of a deferred torch.roll was modified in place (through a plain alias of its storage) "
+                                   "between the roll and the first use of its result; use the result first, or roll a plain tensor")
             self._value = torch.roll(plain(self.source), self.shift, 0)
+            _PENDING_ROLLS.pop(id(self), None)
         return self._value
 
     @classmethod
@@ -195,6 +213,38 @@ def _unwrap(a):
     return a.materialize() if isinstance(a, (LazyOut, LazyRoll)) else a
 
 
+def _version_of(t) -> Optional[int]:
+    try:
+        return t._version
+    except RuntimeError:          # (an inference tensor keeps no version counter)
+        return None
+
+
+def _writes(name: str, kwargs) -> bool:
+    """Does the torch function `name` write one of its arguments (an in-place method, an in-place operator, ``out=``)?"""
+    return (name.endswith("_") and not name.endswith("__")) or name in _INPLACE_DUNDERS or kwargs.get("out") is not None
+
+
+def _materialize_rolls_of(args, kwargs) -> None:
+    """Materialise every pending LazyRoll whose source is (a RollDeferring view of the storage of) one of the deferring arguments of an
+    in-place call, BEFORE the call writes it."""
+    tgt = []
+    tree_map(lambda a: tgt.append(a) if isinstance(a, (LazyOut, RollDeferring)) else None, (args, kwargs))
+    if not tgt:
+        return
+    lazy_srcs = [a for a in tgt if isinstance(a, LazyOut)]
+    with torch._C.DisableTorchFunctionSubclass():
+        ptrs = {a.untyped_storage().data_ptr() for a in tgt if isinstance(a, RollDeferring)}
+    for ref in list(_PENDING_ROLLS.values()):
+        r = ref()
+        if r is None:
+            continue
+        src = r.source
+        if r._value is None and (any(src is a for a in lazy_srcs) or
+                                 (not isinstance(src, LazyOut) and src.untyped_storage().data_ptr() in ptrs)):
+            r.materialize()
+
+
 def _roll_rows_args(args, kwargs):
     """(shift) of a ``roll(x, s, 0)`` call with one integer shift along dim 0, else None."""
     rest = list(args[1:])
@@ -213,7 +263,10 @@ class RollDeferring(torch.Tensor):
     @classmethod
     def __torch_function__(cls, func, types, args=(), kwargs=None):
         kwargs = kwargs or {}
-        if getattr(func, "__name__", "") == "roll" and args and type(args[0]) is RollDeferring:
+        name = getattr(func, "__name__", "")
+        if _PENDING_ROLLS and _writes(name, kwargs):
+            _materialize_rolls_of(args, kwargs)
+        if name == "roll" and args and type(args[0]) is RollDeferring:
             shift = _roll_rows_args(args, kwargs)
             if shift is not None:
                 return LazyRoll(args[0].as_subclass(torch.Tensor), shift)

@@ -331,7 +331,8 @@ class LpSimCLRLoss(CLLoss):
         del z1, z2_con_z1, z3   # unused by the reference as well (losses.py:431)
         # negatives that are the anchors in another order, not computed: RolledRows (callers inside this package) or the deferred
         # torch.roll of a deferred encoder output (lazy.LazyRoll: the reference's own z3_rec = torch.roll(z1_rec, 1, 0))
-        rolled = isinstance(z3_rec, (RolledRows, lazy.LazyRoll)) and z3_rec.source is z1_rec
+        # (a LazyRoll materialised already -- its source was written in place after the roll -- is the roll of the OLD values)
+        rolled = isinstance(z3_rec, (RolledRows, lazy.LazyRoll)) and z3_rec.source is z1_rec and getattr(z3_rec, "_value", None) is None
         if isinstance(z3_rec, (RolledRows, lazy.LazyRoll)) and not (rolled and _sym_enabled() and float(self.p) >= 1.0 and z1_rec.dim() == 2):
             z3_rec, rolled = z3_rec.materialize(), False
         z1_rec, z2_con_z1_rec = lazy.plain(z1_rec), lazy.plain(z2_con_z1_rec)

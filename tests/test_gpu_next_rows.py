@@ -739,14 +739,22 @@ def test_captured_train_step_replays_the_reference_closure(opt_kind):
             d = (q_e.detach() - q_c.detach()).abs().max().item()
             assert d <= 2e-6 * max(1.0, q_e.detach().abs().max().item()), (k, d)
     PARITY.check("dropin_captured", f"{opt_kind} B={B}", "loss after lockstep steps (replay vs eager closure)", got[0], ref[0])
-    # another batch shape: the closure itself runs (and trains)
+    # another batch shape: the closure itself runs (and trains) -- the same step as the eager twin's
     x1 = torch.rand(333, n, generator=g).cuda()
+    odd = (x1, (x1 + 0.05).clamp(0, 1))
     before = [q.detach().clone() for q in f_c.parameters()]
-    out = replay((x1, (x1 + 0.05).clamp(0, 1)), L_c, opt_c)
+    out = replay(odd, L_c, opt_c)
+    ref = step_e(odd, L_e, opt_e)
     assert isinstance(out[0], float) and any(not torch.equal(b, q.detach()) for b, q in zip(before, f_c.parameters()))
-    # and the graph still replays afterwards
+    # and the graph still replays afterwards, in lockstep with the twin
     out2 = replay(batches[0], L_c, opt_c)
-    assert np.isfinite(out2[0])
+    ref2 = step_e(batches[0], L_e, opt_e)
+    for got_, ref_ in ((out, ref), (out2, ref2)):
+        np.testing.assert_allclose(got_[0], ref_[0], rtol=2e-6, atol=0)
+        np.testing.assert_allclose(got_[1], ref_[1], rtol=2e-6, atol=0)
+    for q_e, q_c in zip(f_e.parameters(), f_c.parameters()):
+        d = (q_e.detach() - q_c.detach()).abs().max().item()
+        assert d <= 2e-6 * max(1.0, q_e.detach().abs().max().item()), ("after the fallback step", d)
 
 
 @pytest.mark.gpu

@@ -627,3 +627,45 @@ def test_roll_deferring_view_on_cpu():
     assert torch.equal(lazy.plain(r), torch.roll(t, 1, 0))
     assert type(v + 1) is torch.Tensor and type(torch.roll(v, 1, 1)) is torch.Tensor and torch.equal(torch.roll(v, 1, 1), torch.roll(t, 1, 1))
     assert torch.equal(v.roll(-1, 0) * 1.0, torch.roll(t, -1, 0))
+
+
+@pytest.mark.parametrize("write", ["add_", "iadd", "setitem", "out", "copy_"])
+def test_lazy_roll_of_a_mutated_source_is_the_roll_at_the_call_on_cpu(write):
+    """`r = torch.roll(z, 1, 0)` on a RollDeferring batch (what capture_train_step hands the closure), then an in-place write to `z`: `r` is
+    the roll of the values at the roll call, as torch.roll's result is -- the write materialises the pending roll first.  A write through a
+    plain alias of the storage bypasses the subclass: reading `r` then raises instead of returning the roll of the new values.  The same
+    for a deferred encoder output as the source."""
+    from cl_ica_amd import lazy
+    base = torch.arange(12.0).reshape(6, 2)
+    want = torch.roll(base, 1, 0)
+    rd = base.clone().as_subclass(lazy.RollDeferring)
+    r = torch.roll(rd, 1, 0)
+    assert type(r) is lazy.LazyRoll and r._value is None
+    if write == "add_":
+        rd.add_(1.0)
+    elif write == "iadd":
+        rd += 1.0
+    elif write == "setitem":
+        rd[0] = 100.0
+    elif write == "out":
+        torch.add(rd, 1.0, out=rd)
+    else:
+        rd.copy_(torch.zeros(6, 2))
+    assert not torch.equal(rd.as_subclass(torch.Tensor), base)               # the write happened
+    assert torch.equal(lazy.plain(r), want)
+    # bypassing the subclass: loud, never the roll of the mutated tensor
+    rd2 = base.clone().as_subclass(lazy.RollDeferring)
+    r2 = torch.roll(rd2, 1, 0)
+    rd2.as_subclass(torch.Tensor).mul_(2.0)
+    with pytest.raises(RuntimeError, match="modified in place"):
+        lazy.plain(r2)
+    # a deferred module output as the source
+    w = torch.randn(3, 2)
+
+    class Owner:
+        pass
+    x1 = torch.randn(4, 3)
+    a = lazy.defer(Owner(), x1, lambda x: x @ w, (4, 2), [w])
+    ra = torch.roll(a, 1, 0)
+    a.mul_(-3.0)
+    assert ra._value is not None and torch.equal(lazy.plain(ra), torch.roll(x1 @ w, 1, 0))
