@@ -40,11 +40,17 @@ class DyParts(C.Structure):
                 ("inv_count", C.c_float), ("means", C.c_void_p), ("tick", C.c_void_p)]
 
 
+class MseTarget(C.Structure):
+    """clica_mse_target (include/clica.h): the MSE objective the backward chain's prologue forms dY from."""
+    _fields_ = [("y", C.c_void_p), ("ldy", c_i64), ("target", C.c_void_p), ("ldt", c_i64), ("loss_out", C.c_void_p), ("tick", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", c_size)]
+
+
 class ChainTail(C.Structure):
     """clica_chain_tail (include/clica.h): what the backward chain needs to leave the n-wide layers' weight-gradient slabs."""
     _fields_ = [("a_last", C.c_void_p), ("lda", c_i64), ("x", C.c_void_p), ("ldx", c_i64), ("n_layers", c_i32),
                 ("N", C.POINTER(c_i32)), ("K", C.POINTER(c_i32)), ("wgrad_workspace", C.c_void_p), ("wgrad_workspace_bytes", c_size),
-                ("dy_parts", C.POINTER(DyParts))]
+                ("dy_parts", C.POINTER(DyParts)), ("mse", C.POINTER(MseTarget))]
 
 
 class DotLossDesc(C.Structure):
@@ -82,6 +88,8 @@ SIGNATURES: Dict[str, list] = {
                                     C.c_void_p, c_size, C.c_void_p],
     "clica_lp_loss_bwd_sym_train_parts": [C.POINTER(LpLossDesc), c_f32p, c_i64, c_f32p, c_i64, c_f32p, c_f32p, c_f32p, C.c_void_p,
                                           C.c_void_p, c_size, C.POINTER(DyParts), C.c_void_p],
+    "clica_mse_loss_workspace_bytes": [c_i64, c_i32, C.POINTER(c_size)],
+    "clica_mse_loss_fwd_bwd": [c_f32p, c_i64, c_f32p, c_i64, c_i64, c_i32, c_f32p, c_i64, c_f32p, C.c_void_p, C.c_void_p, c_size, C.c_void_p],
     "clica_dot_loss_workspace_bytes": [C.POINTER(DotLossDesc), C.POINTER(c_size), C.POINTER(c_size)],
     "clica_dot_loss_fwd": [C.POINTER(DotLossDesc)] + _LOSS_FWD,
     "clica_dot_loss_bwd": [C.POINTER(DotLossDesc)] + _LOSS_BWD,

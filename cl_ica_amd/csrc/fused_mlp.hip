@@ -21,6 +21,7 @@
 #include "wgrad_shared.h"
 #include "sampler_dev.h"
 #include "lp_guard.h"
+#include "mse.h"
 #include <stdlib.h>
 
 namespace clica {
@@ -893,6 +894,12 @@ struct SplitArgs {
     int boff, K; long long off3, ent3;
     int pad[2];
   } q[MAXL];
+  // (last: the fields above keep their kernel-argument offsets)  The launch's input is the encoder OUTPUT y of a step on the MSE objective (clica_mse_target, include/clica.h): the prologue forms
+  // dY = (y - t) * scale for its rows, writes it for the tail and the last layer's weight gradient, feeds it to the first link, and every
+  // wave adds its share of sum (y - t)^2 to the launch's deterministic reduction (mse.h).  t == nullptr: plain input.
+  struct Mse {
+    const float* t; long long ldt; float* dy; long long lddy; float scale, inv_count; float* loss; int* tick; float* part; int* arrive;
+  } mse;
 };
 #ifndef CLICA_SPLIT_WARM_NEXT
 #define CLICA_SPLIT_WARM_NEXT 12                 // 12: also a 500 x 500 layer that follows directly (1.5 MB per XCD); 3: short layers only
@@ -1544,6 +1551,8 @@ __global__ __launch_bounds__(THREADS) void mlp_split_k(SplitArgs a) {
       // the input rows: requested for up to four values per thread before the first is used
       constexpr int XIT = 4;
       const SplitArgs::DyParts& P = a.parts;
+      const SplitArgs::Mse& E = a.mse;
+      float mse_sq = 0.f;
       int nsp = 0;
       if (P.part) {
         nsp = P.nsplit;
@@ -1586,6 +1595,12 @@ __global__ __launch_bounds__(THREADS) void mlp_split_k(SplitArgs a) {
             }
             P.dy[(row0 + r) * P.ldy + k] = xv[u];
           }
+          if (E.t && ok) {                             // clica_mse_loss_fwd_bwd's arithmetic: the same dY bits
+            const float d = xv[u] - E.t[(row0 + r) * E.ldt + k];
+            mse_sq = fmaf(d, d, mse_sq);
+            xv[u] = d * E.scale;
+            E.dy[(row0 + r) * E.lddy + k] = xv[u];
+          }
         }
 #pragma unroll
         for (int u = 0; u < XIT; ++u) {
@@ -1593,6 +1608,8 @@ __global__ __launch_bounds__(THREADS) void mlp_split_k(SplitArgs a) {
           if (idx < ROWS * K16) { const int r = idx / K16; store_split(r, idx - r * K16, xv[u]); }
         }
       }
+      if (E.t)
+        mse::wave_arrive(mse_sq, E.part, (int)blockIdx.x * WAVES + wave, (int)gridDim.x * WAVES, E.arrive, E.loss, E.inv_count, E.tick);
 #pragma unroll
       for (int u = 0; u < BIAS_IT; ++u) { const int idx = threadIdx.x + u * THREADS; if (idx < btotal) bias_lds[idx] = bv[u]; }
     }
@@ -1883,7 +1900,11 @@ __global__ __launch_bounds__(THREADS) void mlp_split_k(SplitArgs a) {
     __syncthreads();
   }
   if constexpr (AR == 1) {        // (behind the last layer's closing barrier) this workgroup's slot of the maxima
-    if (blockIdx.x < a.cap_wg && threadIdx.x < Split16State::NT) a.part_t[(size_t)threadIdx.x * kS16CapWG + blockIdx.x] = amax_lds[threadIdx.x];
+    // (an unscaled last output -- fp32 only, its scale is never applied -- leaves 0, "not produced": the update keeps that scale and does not
+    //  hold the tensor's magnitude against it.  A chain whose input grows with the encoder's output -- the MSE objective's dY -- would
+    //  otherwise have its fp32 dZ_0 raise the update's unannounced-overflow flag on the first healthy step after a withheld one.)
+    if (blockIdx.x < a.cap_wg && threadIdx.x < Split16State::NT)
+      a.part_t[(size_t)threadIdx.x * kS16CapWG + blockIdx.x] = ((int)threadIdx.x == g.L && a.last_unscaled) ? 0u : amax_lds[threadIdx.x];
     if (blockIdx.x == 0 && (int)threadIdx.x <= g.L) a.count_t[threadIdx.x] = gridDim.x < a.cap_wg ? gridDim.x : a.cap_wg;
     // the guard: tensor t of this launch (0: its input, l + 1: output of layer l) was cut to fp16 on scale s_t[t]; a maximum beyond the
     // alarm (or a non-finite one) in this workgroup's rows poisons the step (the last layer's output stays fp32 when nobody re-splits it)
@@ -2300,6 +2321,23 @@ static int mlp_dgrad_split_impl(const float* dY, int64_t lddy, int64_t M, int32_
                       (long long)dp.rows, dp.n, (long long)M, K[0]);
       a.parts = SplitArgs::DyParts{dp.part, dp.nsplit, dp.nsplit_alt > 0 ? dp.nsplit_alt : dp.nsplit, dp.np, dp.n, dp.rows, dp.guard_words, dp.guard_limit,
                                    dp.blocksums, dp.nblocks, dp.inv_count, dp.means, dp.tick, const_cast<float*>(dY), lddy};
+    }
+    if (tail->mse) {
+      static_assert(ROWS == mse::kFoldRows && WAVES <= mse::kFoldWaves, "mse.h sizes the workspace for the chain's panels");
+      const clica_mse_target& m = *tail->mse;
+      const int n = K[0];
+      CLICA_CHECK_ARG(!tail->dy_parts, "clica_mlp_dgrad_split_tail: mse and dy_parts exclude each other");
+      CLICA_CHECK_ARG(m.y && m.target && m.loss_out && m.workspace, "clica_mlp_dgrad_split_tail: NULL pointer in the mse descriptor");
+      CLICA_CHECK_ARG(m.ldy >= n && m.ldt >= n, "clica_mlp_dgrad_split_tail: mse leading dimension below n=%d (ldy=%lld ldt=%lld)", n,
+                      (long long)m.ldy, (long long)m.ldt);
+      CLICA_CHECK_ARG((reinterpret_cast<uintptr_t>(m.workspace) & 15) == 0 && m.workspace_bytes >= mse::workspace_bytes(M, n),
+                      "clica_mlp_dgrad_split_tail: mse workspace of %zu bytes, %zu needed (clica_mse_loss_workspace_bytes), 16-byte aligned",
+                      m.workspace_bytes, mse::workspace_bytes(M, n));
+      const double count = (double)M * (double)n;
+      char* ws = static_cast<char*>(m.workspace);
+      g.X = m.y; g.ldx = m.ldy;                  // the prologue reads y; dY is the launch's output
+      a.mse = SplitArgs::Mse{m.target, m.ldt, const_cast<float*>(dY), lddy, (float)(2.0 / count), (float)(1.0 / count), m.loss_out, m.tick,
+                             reinterpret_cast<float*>(ws + mse::kHeaderBytes), reinterpret_cast<int*>(ws)};
     }
   }
   return launch_split(a, state16 ? 1 : 0, stream, state16 ? "clica_mlp_dgrad_split16" : "clica_mlp_dgrad_split");

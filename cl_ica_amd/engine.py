@@ -31,7 +31,7 @@ from contextlib import nullcontext as _nullctx
 
 from .distributed import GradBuckets
 
-__all__ = ["SamplerSpec", "ContrastiveTrainer"]
+__all__ = ["SamplerSpec", "ContrastiveTrainer", "SupervisedTrainer"]
 
 
 @dataclass
@@ -164,7 +164,7 @@ class ContrastiveTrainer:
             shapes = [tuple(lin.weight.shape) for lin in self.linears]
             mk = ops.mlp_wgrad_split_workspace if self.split_wgrad else ops.mlp_wgrad_workspace
             for part in (shapes[self._half:], shapes[:self._half]):
-                w = mk(2 * self.B, part, self.device)
+                w = mk(self._enc_rows(), part, self.device)
                 if w.numel() > self.group_ws.numel():
                     self.group_ws = w
         slices = list(self._layer_slices)
@@ -226,12 +226,16 @@ class ContrastiveTrainer:
                 self._layer_slices[0] = (min(lo, o), max(hi, o + (k + 3) // 4 * 4))
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
 
+    def _enc_rows(self) -> int:
+        """Rows the encoder runs on per step: the pair z, z~ stacked."""
+        return 2 * self.B
+
     def _allocate(self):
         dev, B, n = self.device, self.B, self.n
-        R = 2 * B
+        R = self._enc_rows()
         f32 = dict(dtype=torch.float32, device=dev)
-        self.z = torch.empty((R, n), **f32)            # rows [0,B): z ; [B,2B): z~
-        self.x = torch.empty((R, n), **f32)            # g(z), g(z~)
+        self.z = torch.empty((2 * B, n), **f32)        # rows [0,B): z ; [B,2B): z~  (the sampler draws the pair)
+        self.x = torch.empty((R, n), **f32)            # g(z), g(z~): the encoder's input rows
         widths = [lin.out_features for lin in self.linears]
         self.acts = [torch.empty((R, w), **f32) for w in widths]     # post-activation outputs; last = pre-head
         self.y = torch.empty((R, n), **f32) if self.head is not None else self.acts[-1]
@@ -239,24 +243,7 @@ class ContrastiveTrainer:
         wmax = max(widths + [n])
         self.dbuf = [torch.empty((R, wmax), **f32) for _ in range(3)]
         self.side_stream = torch.cuda.Stream(device=dev) if (dev.type == "cuda" and self.overlap_backward) else None
-        self.dy = torch.empty((R, n), **f32)
-        self.loss_out = torch.empty(3 * B + 3, **f32)
-        Bg = B * self.world * self.emulate_pool * self.dry_ranks
-        pooled = self.dp or self.emulate_pool > 1
-        self.z_all = torch.empty((Bg, n), **f32) if pooled else None
-        self.lse_all = torch.empty((Bg,), **f32) if pooled else None
-        self.desc = _lib.LpLossDesc(B=B, B3=Bg, n=n, p=self.p, tau=self.tau, alpha=self.alpha, compat=1, pow=1)
-        fb, bb = C.c_size_t(), C.c_size_t()
-        _lib.check(_lib.load().clica_lp_loss_workspace_bytes(C.byref(self.desc), C.byref(fb), C.byref(bb)), "workspace")
-        tb = C.c_size_t()
-        self.loss_train = self.p >= 1                  # fused training pair of loss entry points
-        if self.loss_train:
-            _lib.check(_lib.load().clica_lp_loss_train_workspace_bytes(C.byref(self.desc), C.byref(tb)), "train workspace")
-        self.loss_ws = torch.zeros(max(fb.value, bb.value, tb.value), dtype=torch.uint8, device=dev)
-        # the step / RNG counter is advanced by the loss backward's reduction launch (all samplers of the step have run by then)
-        # instead of a separate one-thread launch at the end; Adam then takes t = counter
-        self.early_tick = self.loss_train
-        self._ticked = False
+        self._allocate_loss(R)
         nb = C.c_size_t(); need = 0
         for lin in self.linears:
             _lib.check(_lib.load().clica_linear_wgrad_workspace_bytes(R, lin.out_features, lin.in_features, C.byref(nb)), "wgrad ws")
@@ -335,11 +322,35 @@ class ContrastiveTrainer:
             self.head_learnable = isinstance(hp, nn.Parameter)
             self.dpre = torch.empty((R, n), **f32)
 
+    def _allocate_loss(self, R):
+        """Buffers of the objective: the Lp-InfoNCE loss of the pair (outputs, workspaces, the negatives pool under data parallelism)."""
+        dev, B, n = self.device, self.B, self.n
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.dy = torch.empty((R, n), **f32)
+        self.loss_out = torch.empty(3 * B + 3, **f32)
+        Bg = B * self.world * self.emulate_pool * self.dry_ranks
+        pooled = self.dp or self.emulate_pool > 1
+        self.z_all = torch.empty((Bg, n), **f32) if pooled else None
+        self.lse_all = torch.empty((Bg,), **f32) if pooled else None
+        self.desc = _lib.LpLossDesc(B=B, B3=Bg, n=n, p=self.p, tau=self.tau, alpha=self.alpha, compat=1, pow=1)
+        fb, bb = C.c_size_t(), C.c_size_t()
+        _lib.check(_lib.load().clica_lp_loss_workspace_bytes(C.byref(self.desc), C.byref(fb), C.byref(bb)), "workspace")
+        tb = C.c_size_t()
+        self.loss_train = self.p >= 1                  # fused training pair of loss entry points
+        if self.loss_train:
+            _lib.check(_lib.load().clica_lp_loss_train_workspace_bytes(C.byref(self.desc), C.byref(tb)), "train workspace")
+        self.loss_ws = torch.zeros(max(fb.value, bb.value, tb.value), dtype=torch.uint8, device=dev)
+        # the step / RNG counter is advanced by the loss backward's reduction launch (all samplers of the step have run by then)
+        # instead of a separate one-thread launch at the end; Adam then takes t = counter
+        self.early_tick = self.loss_train
+        self._ticked = False
+
+
     def _init_wide_ones(self):
         """The fused epilogues of the wide chain never touch the constant-1 column of the N-planes they fill: written once here."""
         if not getattr(self, "chain", None):
             return
-        L, R = len(self.linears), 2 * self.B
+        L, R = len(self.linears), self._enc_rows()
         widths = [lin.out_features for lin in self.linears]
         for l in self.chain:
             if l + 1 < L and self.wide_kinds[l + 1] == 0:
@@ -377,7 +388,7 @@ class ContrastiveTrainer:
         """x = g(z): its own launch, unless the fused forward runs the mixing net in its prologue."""
         self._x_pending = self.mix_in_forward
         if not self.mix_in_forward:
-            ops.mixing_fwd(self.z, self.gW, self.g_slope, out=self.x, act_kind=self.g_act_kind)
+            ops.mixing_fwd(self.z[:self.x.shape[0]], self.gW, self.g_slope, out=self.x, act_kind=self.g_act_kind)
 
     # -------------------------------------------------------------------------------- step pieces
     def _pack_sample_merged(self) -> bool:
@@ -423,7 +434,7 @@ class ContrastiveTrainer:
                 self.pack()
             mix = None
             if self._x_pending:          # latents in, x = g(z) computed in the kernel prologue and stored to self.x
-                cur, mix, self._x_pending = self.z, (self.gW, self.g_slope, self.x), False
+                cur, mix, self._x_pending = self.z[:self.x.shape[0]], (self.gW, self.g_slope, self.x), False
             if self.split_bf16:
                 ops.mlp_fwd_split(cur, ws, [lin.bias for lin in self.linears], self.acts_out, self.packed, self.slope,
                                   signmasks=self.signmasks, mix=mix, planes=self.act_planes if self.split_wgrad else None, state=self.s16)
@@ -595,11 +606,13 @@ class ContrastiveTrainer:
                 # slabs (clica_mlp_dgrad_split_tail) -- weight_grads() then needs no tiny-dimension launch
                 if self._chain_tail_ok():
                     tail = dict(a_last=self.acts_out[L - 2], x=self.x, shapes=[tuple(lin.weight.shape) for lin in self.linears], ws=self.group_ws,
-                                dy_parts=getattr(self, "_dy_parts", None))
+                                dy_parts=getattr(self, "_dy_parts", None), mse=getattr(self, "_mse_fold", None))
                     self._tail_ready = True
             if getattr(self, "_dy_parts", None) is not None and (tail is None or g is not self.dy):
                 raise _lib.ClicaError("engine: the loss left its partials for the backward chain, but the chain does not run with its tail on dy")
-            self._dy_parts = None
+            if getattr(self, "_mse_fold", None) is not None and (tail is None or g is not self.dy):
+                raise _lib.ClicaError("engine: the MSE objective was left to the backward chain, but the chain does not run with its tail on dy")
+            self._dy_parts = self._mse_fold = None
             ops.mlp_dgrad_chain_split(g, ws, self.packed_t, [self.dz_out[l - 1] for l in chain], self.slope,
                                       masks_chain=[self.signmasks[l - 1] for l in chain],
                                       planes=[self.dz_planes[l - 1] for l in chain] if self.split_wgrad else None, state=self.s16, tail=tail)
@@ -932,13 +945,16 @@ class ContrastiveTrainer:
             ops.PARAM_EPOCH += 1
         else:
             self._step_body(True)
-        return self.loss_out[3 * self.B:]
+        return self._result()
 
     def step_injected(self, z1, z2):
         self._check_external_writes()
         self.inject(z1, z2)
         self._step_body(False)
         ops.PARAM_EPOCH += 1
+        return self._result()
+
+    def _result(self) -> torch.Tensor:
         return self.loss_out[3 * self.B:]
 
     def capture(self, warmup: int = 3):
@@ -1043,3 +1059,87 @@ class ContrastiveTrainer:
     @property
     def steps_done(self) -> int:
         return int(self.step_dev.item())
+
+
+class SupervisedTrainer(ContrastiveTrainer):
+    """Fused, HBM-resident step of the SUPERVISED phase of main_mlp.py (the first of the default ``test_list = [True, False]``,
+    :249-255): ``F.mse_loss(f(g(z1)), z1)`` (:274-276), backward, Adam -- no autograd, no host sync.
+
+    The contrastive step's machinery on the B rows of z1 only (the reference also evaluates h(z2) and never reads it: not computed
+    here): the same sampler launch (merged with the weight pack in f16x2), the mixing net in the forward's prologue, the whole-stack
+    forward, the backward chain with its tail, the weight gradients with Adam folded in, the f16x2 scales and their guard, capture.
+    The objective is row-local, dY = 2 (y - z1) / (B n): where the chain runs with its tail on dY (whole-stack split path, no output
+    head) the chain's prologue forms dY and the loss itself (clica_mse_target), otherwise one launch of clica_mse_loss_fwd_bwd sits
+    between the forward (and head) and the backward.  Either launch advances the step / RNG counter, as the loss backward does in
+    the contrastive step.  One rank only."""
+
+    # test hook (class attribute, tests/test_gpu_supervised.py): the chain's prologue forms dY (False: the stand-alone launch)
+    fold_mse = True
+
+    def __init__(self, f: nn.Sequential, g_weights: torch.Tensor, sampler: SamplerSpec, batch_size: int,
+                 lr: float = 1e-4, g_slope: float = 0.2, betas=(0.9, 0.999), eps: float = 1e-8, device=None,
+                 process_group: Optional[dist.ProcessGroup] = None, bucket_bytes: int = 8 << 20,
+                 force_collectives: bool = False, overlap_backward: bool = True, fused_forward: bool = True,
+                 split_bf16: Optional[bool] = None, g_act_kind: int = 0, emulate_pool_ranks: int = 1, dry_ranks: int = 1,
+                 split_arith: Optional[str] = None):
+        world = dist.get_world_size(process_group) if dist.is_initialized() else 1
+        if world > 1 or force_collectives or int(dry_ranks) > 1 or int(emulate_pool_ranks) > 1:
+            raise NotImplementedError("SupervisedTrainer runs on one rank: data parallelism of the supervised step is not implemented "
+                                      "(train_mlp runs that phase through autograd_train_step when world > 1)")
+        super().__init__(f, g_weights, sampler, batch_size, p=2, lr=lr, g_slope=g_slope, betas=betas, eps=eps, device=device,
+                         process_group=process_group, bucket_bytes=bucket_bytes, overlap_backward=overlap_backward,
+                         fused_forward=fused_forward, split_bf16=split_bf16, g_act_kind=g_act_kind, split_arith=split_arith)
+        self.p = self.tau = self.alpha = None        # (no contrastive loss in this step)
+
+    def _enc_rows(self) -> int:
+        return self.B
+
+    def _allocate_loss(self, R):
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self.dy = torch.empty((R, self.n), **f32)
+        self.loss_out = torch.zeros(1, **f32)
+        self.z_all = self.lse_all = self.desc = None
+        self.loss_train = False
+        self.loss_ws = ops.mse_loss_workspace(R, self.n, self.device)     # arrival counter + partials (zero between launches)
+        self.early_tick = True           # the objective's launch (or the chain's prologue) advances the step / RNG counter
+        self._ticked = False
+        self._mse_fold = None
+
+    def inject(self, z1: torch.Tensor, z2: Optional[torch.Tensor] = None):
+        """Use caller-provided latents z1 (parity tests); `z2` is accepted for symmetry with the contrastive step and not used."""
+        self.z[:self.B].copy_(z1)
+        self._mix()
+
+    def step_injected(self, z1, z2=None):
+        return super().step_injected(z1, z2)
+
+    def _result(self) -> torch.Tensor:
+        return self.loss_out
+
+    def _chain_takes_mse(self) -> bool:
+        """Will THIS step's backward chain run with its tail directly on dY?  Then its prologue forms dY and the loss."""
+        if not self.fold_mse or not getattr(self, "_in_step", False):
+            return False
+        if self.head is not None or not (self.split_bf16 and self.split_wgrad and self.fused_backward):
+            return False
+        return self._adam_folds_into_wgrad() and self._chain_tail_ok()
+
+    def loss_forward_backward(self):
+        """loss = mean((y - z1)^2), dY = 2 (y - z1) / (B n): left to the backward chain's prologue, or one launch here."""
+        target = self.z[:self.B]
+        tick = self.step_dev if self.early_tick else None
+        self._mse_fold = None
+        if self._chain_takes_mse():
+            self._mse_fold = dict(y=self.y, target=target, loss_out=self.loss_out, ws=self.loss_ws, tick=tick)
+            self._mse_taken = getattr(self, "_mse_taken", 0) + 1       # (tests: which path a trainer took)
+        else:
+            ops.mse_loss_fwd_bwd(self.y, target, dy=self.dy, loss_out=self.loss_out, ws=self.loss_ws, tick_counter=tick)
+        self._ticked = self.early_tick
+
+    def loss_spread(self) -> float:
+        return 0.0
+
+    def plan_summary(self) -> dict:
+        return dict(world=1, batch_per_rank=self.B, encoder_rows=self._enc_rows(), objective="mse",
+                    encoder_path="whole-stack" if self.fused_forward else "per-layer", split_bf16=bool(self.split_bf16),
+                    graph_captured=self.graph is not None)

@@ -392,9 +392,16 @@ def mlp_dgrad_chain_split(dy: torch.Tensor, weights_chain, packed_split_t: torch
         Le = len(shapes)
         N32, K32 = (C.c_int32 * Le)(*[sh[0] for sh in shapes]), (C.c_int32 * Le)(*[sh[1] for sh in shapes])
         parts = tail.get("dy_parts")          # _lib.DyParts filled by clica_lp_loss_bwd_sym_train_parts: the chain's prologue finishes dy
+        mse = tail.get("mse")                 # dict(y, target, loss_out, ws[, tick]): the chain's prologue forms dy from the MSE objective
+        mse_desc = None
+        if mse is not None:
+            (yy, ldy), (tt, ldt) = _mat("y", mse["y"]), _mat("target", mse["target"])
+            mse_desc = _lib.MseTarget(y=yy.data_ptr(), ldy=ldy, target=tt.data_ptr(), ldt=ldt, loss_out=mse["loss_out"].data_ptr(),
+                                      tick=ptr(mse.get("tick")), workspace=mse["ws"].data_ptr(), workspace_bytes=mse["ws"].numel())
         desc = _lib.ChainTail(a_last=al.data_ptr(), lda=lda, x=xx.data_ptr(), ldx=ldx, n_layers=Le, N=N32, K=K32,
                               wgrad_workspace=tail["ws"].data_ptr(), wgrad_workspace_bytes=tail["ws"].numel(),
-                              dy_parts=C.pointer(parts) if parts is not None else None)
+                              dy_parts=C.pointer(parts) if parts is not None else None,
+                              mse=C.pointer(mse_desc) if mse_desc is not None else None)
         check(load().clica_mlp_dgrad_split_tail(*args, None if state is None else state.buf.data_ptr(), C.byref(desc), stream_ptr()),
               "clica_mlp_dgrad_split_tail")
     elif state is None:
@@ -689,6 +696,36 @@ def stamp_intervals_us(slot: torch.Tensor):
     v = slot.cpu()
     n = min(int(v[0]), (v.numel() - 1) // 2)
     return [(int(v[2 + 2 * i]) - int(v[1 + 2 * i])) / 100.0 for i in range(n)]
+
+
+# ------------------------------------------------------------------------------- MSE objective
+def mse_loss_workspace(M: int, n: int, device) -> torch.Tensor:
+    """Zeroed workspace of clica_mse_loss_fwd_bwd / the backward chain's MSE prologue for M x n (its arrival counter must start at zero)."""
+    nb = C.c_size_t()
+    check(load().clica_mse_loss_workspace_bytes(int(M), int(n), C.byref(nb)), "clica_mse_loss_workspace_bytes")
+    return torch.zeros(nb.value, dtype=torch.uint8, device=device)
+
+
+def mse_loss_fwd_bwd(y: torch.Tensor, target: torch.Tensor, dy: Optional[torch.Tensor] = None, loss_out: Optional[torch.Tensor] = None,
+                     ws: Optional[torch.Tensor] = None, tick_counter: Optional[torch.Tensor] = None):
+    """loss = mean((y - target)^2) (F.mse_loss) and dy = 2 (y - target) / y.numel() in one launch, deterministic
+    (clica_mse_loss_fwd_bwd).  Strided row views pass without a copy.  Returns (loss_out [1] device tensor, dy)."""
+    (y, ldy), (target, ldt) = _mat("y", y), _mat("target", target)
+    if target.shape != y.shape:
+        raise ValueError(f"target {tuple(target.shape)} does not match y {tuple(y.shape)}")
+    M, n = y.shape
+    dy = torch.empty((M, n), dtype=torch.float32, device=y.device) if dy is None else dy
+    loss_out = torch.empty(1, dtype=torch.float32, device=y.device) if loss_out is None else loss_out
+    if ws is None:
+        nb = C.c_size_t()
+        check(load().clica_mse_loss_workspace_bytes(M, n, C.byref(nb)), "clica_mse_loss_workspace_bytes")
+        ws = workspace("mse_loss", nb.value, y.device)
+    (dyv, lddy) = _mat("dy", dy)
+    if dyv.data_ptr() != dy.data_ptr():
+        raise ValueError("dy must be a row-major (strided) view")
+    check(load().clica_mse_loss_fwd_bwd(y.data_ptr(), ldy, target.data_ptr(), ldt, M, n, dy.data_ptr(), lddy, loss_out.data_ptr(),
+                                        ptr(tick_counter), ws.data_ptr(), ws.numel(), stream_ptr()), "clica_mse_loss_fwd_bwd")
+    return loss_out, dy
 
 
 def tick(counter: torch.Tensor):

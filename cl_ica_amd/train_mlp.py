@@ -7,7 +7,8 @@ unsupervised), same log lines and checkpoints (g.pth, sup_f.pth, unsup_f.pth).
 
 The unsupervised phase (the hot path) runs on ``ContrastiveTrainer``: on-device sampling, fused fp32-MFMA
 encoder, tiled Lp-InfoNCE, fused Adam, replayed from a HIP graph on one GPU; with several ranks each GPU
-trains on its own batch against the all-gathered negatives pool.
+trains on its own batch against the all-gathered negatives pool.  On one GPU the supervised phase runs on
+``SupervisedTrainer``: the same step with the MSE objective on the B rows of z1.
 """
 from __future__ import annotations
 
@@ -22,7 +23,7 @@ import torch.nn.functional as F
 from . import disentanglement_utils as du
 from . import encoders, invertible_network_utils, latent_spaces, losses, spaces
 from .distributed import gather_negatives, init_from_env
-from .engine import ContrastiveTrainer, SamplerSpec
+from .engine import ContrastiveTrainer, SamplerSpec, SupervisedTrainer
 from .optim import Adam as FlatAdam
 
 # (flag, type, default, help) -- the reference's CLI surface
@@ -116,7 +117,8 @@ def evaluate(h, latent_space, n_samples=4096):
 def autograd_train_step(h, loss, optimizer, z1, z2, supervised: bool, world: int = 1):
     """The reference's ``train_step`` verbatim in structure (main_mlp.py:258-285) on the drop-in modules, for the phases the
     fused engine does not cover: the SUPERVISED phase (``test = True``: ``F.mse_loss(z1_rec, z1)``, :274-276 -- the first of the
-    default ``test_list = [True, False]``) and p = 0 (SimCLRLoss).  Returns the 0-dim loss tensor (no host sync)."""
+    default ``test_list = [True, False]``) under data parallelism and p = 0 (SimCLRLoss).  Returns the 0-dim loss tensor (no host
+    sync)."""
     optimizer.zero_grad()
     z1_rec, z2_rec = h(z1), h(z2)
     # negatives = all z1_rec of the (global) batch: roll on one rank, autograd-aware all-gather on several
@@ -168,6 +170,8 @@ def _main(argv=None):
     phases = [False] if args.only_unsupervised else ([True] if args.only_supervised else [True, False])
     total_loss_values = None
     f = None
+    contrastive_engine = False
+    supervised_engine = None
     for supervised in phases:
         log(f"supervised test: {supervised}")
         if args.box_norm:
@@ -183,16 +187,22 @@ def _main(argv=None):
         h = lambda z: f(g(z))   # noqa: E731
         if total_loss_values is None or not args.resume_training:
             total_loss_values, lin_scores, perm_scores = [], [], []
-        fused = (not supervised) and args.p != 0
-        if fused:
+        fused = (world == 1) if supervised else args.p != 0
+        contrastive_engine = fused and not supervised
+        if fused and supervised:
+            trainer = SupervisedTrainer(f, g.weight_stack(), spec, batch_size=args.batch_size, lr=args.lr, g_slope=g.slope,
+                                        g_act_kind=g.act_kind, device=device)
+            if not args.no_graph:
+                trainer.capture()
+        elif fused:
             trainer = ContrastiveTrainer(f, g.weight_stack(), spec, batch_size=args.batch_size, p=args.p, tau=args.tau,
                                          lr=args.lr, g_slope=g.slope, g_act_kind=g.act_kind, device=device,
                                          process_group=None if world == 1 else torch.distributed.group.WORLD)
             if world == 1 and not args.no_graph:
                 trainer.capture()
         else:
-            # supervised / p == 0 phases: autograd over the drop-in modules; flat-arena HIP Adam whose gradient arena is
-            # all-reduced under data parallelism (its 1/world average is applied inside the Adam launch)
+            # supervised phase under data parallelism / p == 0: autograd over the drop-in modules; flat-arena HIP Adam whose gradient
+            # arena is all-reduced under data parallelism (its 1/world average is applied inside the Adam launch)
             if world > 1:
                 for prm in f.parameters():
                     torch.distributed.broadcast(prm.data, src=0)
@@ -225,7 +235,7 @@ def _main(argv=None):
                     if ga["new_skipped"]:
                         log(f"note: the f16x2 guard withheld {ga['new_skipped']} step(s) since the last log point (redone on fresh scales; "
                             f"{ga['skipped']} in total)")
-                if fused and not getattr(trainer, "_guard_noted", False):
+                if contrastive_engine and not getattr(trainer, "_guard_noted", False):
                     gs = trainer.loss_guard()          # (nothing to do: the library's device-side guard switches per step, include/clica.h)
                     if gs["limit"] > 0 and gs["last_spread"] > gs["limit"]:
                         trainer._guard_noted = True
@@ -242,6 +252,13 @@ def _main(argv=None):
                 pending.append(trainer.step()[0].clone())
         if pending:
             total_loss_values += [float(v) for v in torch.stack(pending).cpu()]
+        if fused and supervised:      # what the supervised phase ran on: part of the run's record (main()'s `supervised_engine`)
+            st, ga = trainer.arith_state(), trainer.check_arith()
+            supervised_engine = dict(arith=st.get("arith"), f16_flags=st.get("flags"), f16_steps_withheld=ga["skipped"],
+                                     steps_applied=trainer.steps_done - applied0, graph=trainer.graph is not None,
+                                     last_loss=total_loss_values[-1] if total_loss_values else None)
+            log(f"supervised engine: encoder arithmetic {st.get('arith')}" +
+                (f", scale flags {st.get('flags')}, steps withheld by the guard {ga['skipped']}" if "flags" in st else ""))
         if args.save_dir and rank == 0:
             torch.save(f.state_dict(), os.path.join(args.save_dir, "{}_f.pth".format("sup" if supervised else "unsup")))
 
@@ -255,7 +272,7 @@ def _main(argv=None):
             (pm, _), _ = du.permutation_disentanglement(z1, z1_rec, mode="pearson", solver="munkres", rescaling=True)
             final_lin.append(l); final_perm.append(pm)
     engine_state = None
-    if fused:      # what the engine ran on (f16x2 scales / overflow flag, the loss guard's counters): part of the run's record
+    if contrastive_engine:      # what the engine ran on (f16x2 scales / overflow flag, the loss guard's counters): part of the run's record
         st, gs, ga = trainer.arith_state(), trainer.loss_guard(), trainer.check_arith()
         engine_state = dict(arith=st.get("arith"), f16_flags=st.get("flags"), f16_steps_withheld=ga["skipped"], loss_max_spread=gs["max_spread"],
                             loss_spread_limit=gs["limit"], loss_fallback_steps=gs["fallback_steps"])
@@ -265,7 +282,8 @@ def _main(argv=None):
     log("perm mean: {} std: {}".format(np.mean(final_perm), np.std(final_perm)))
     if world > 1:
         torch.distributed.destroy_process_group()
-    return dict(linear=float(np.mean(final_lin)), perm=float(np.mean(final_perm)), losses=total_loss_values, engine=engine_state)
+    return dict(linear=float(np.mean(final_lin)), perm=float(np.mean(final_perm)), losses=total_loss_values, engine=engine_state,
+                supervised_engine=supervised_engine)
 
 
 if __name__ == "__main__":

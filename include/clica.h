@@ -459,12 +459,34 @@ int clica_mlp_wgrad_split16(int64_t M, int32_t n_layers, const void* const* dZ_p
  * slabs go where that call's plan expects them).  The last link must write its fp32 output.  clica_mlp_chain_tail_supported: first
  * and last layer of the tiny-dimension kind with K[0] <= 15, N[0] <= 128, N[L-1] <= 16, K[L-1] <= 127 (get_mlp's n -> 10 n ... 10 n -> n
  * up to n = 12; encoders.py:36-48). */
+/* Mean-squared-error objective -- F.mse_loss(z1_rec, z1), the supervised phase of /root/reference/main_mlp.py:274-276:
+ *   loss = mean over all M x n elements of (y - t)^2,   dY = 2 (y - t) / (M n)      (rows strided by ldy / ldt / lddy)
+ * One launch; deterministic: every wave leaves a partial sum in the workspace and the last to arrive (an arrival counter in the
+ * workspace, put back to zero by the launch itself: graph replays need no reset) adds them in a fixed order and writes the mean to
+ * loss_out[0].  tick_counter: NULL, or a device counter that launch advances by 1.  The workspace (clica_mse_loss_workspace_bytes,
+ * 16-byte aligned) is zeroed once before its first use; one workspace serves one launch at a time. */
+int clica_mse_loss_workspace_bytes(int64_t M, int32_t n, size_t* bytes);
+int clica_mse_loss_fwd_bwd(const float* y, int64_t ldy, const float* target, int64_t ldt, int64_t M, int32_t n,
+                           float* dY, int64_t lddy, float* loss_out, int32_t* tick_counter, void* workspace, size_t workspace_bytes,
+                           clica_stream_t stream);
+/* The same objective folded into the backward chain (clica_chain_tail.mse): the chain's prologue reads y and the target rows of its
+ * 48-row panel, forms dY (written to the chain's dY argument, which is then an OUTPUT: the tail and the last layer's weight gradient
+ * read it) and feeds it to the first link -- in the f16x2 arithmetic its measured maximum sets the chain input's scale as a
+ * loss-produced dY does -- and adds the panel's share of the loss; the last wave to arrive writes the mean, as above (same workspace
+ * layout, same dY bits as clica_mse_loss_fwd_bwd). */
+typedef struct clica_mse_target {
+  const float* y; int64_t ldy;           /* [M][n] fp32 output of the encoder's last layer */
+  const float* target; int64_t ldt;      /* [M][n] */
+  float* loss_out; int32_t* tick;        /* tick: NULL, or a device counter to advance by 1 */
+  void* workspace; size_t workspace_bytes;
+} clica_mse_target;
 typedef struct clica_chain_tail {
   const float* a_last; int64_t lda;      /* [M][K[L-1]] input of the last layer */
   const float* x; int64_t ldx;           /* [M][K[0]]   encoder input */
   int32_t n_layers; const int32_t* N; const int32_t* K;
   void* wgrad_workspace; size_t wgrad_workspace_bytes;
   const clica_lp_dy_parts* dy_parts;     /* NULL, or: dY (which must be writable) still lacks the pair sweep's partials -- see clica_lp_dy_parts */
+  const clica_mse_target* mse;           /* NULL, or: dY is formed by the chain from the MSE objective (clica_mse_target); excludes dy_parts */
 } clica_chain_tail;
 int clica_mlp_chain_tail_supported(int32_t n_layers, const int32_t* N, const int32_t* K, int32_t* supported);
 /* state == NULL: bf16x3 (clica_mlp_dgrad_split), else f16x2 (clica_mlp_dgrad_split16) */
