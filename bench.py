@@ -17,7 +17,8 @@ operand split exactly into three bf16 pieces, six piece products, fp32 accumulat
 kernels' level) for the forward stack, the backward data chain and the weight gradients.  `dtype` says so; the `native_fp32`
 leg is the same step on the fp32-MFMA kernels (`--native-fp32` makes that the headline instead).
 
-Besides the contract fields the JSON line carries
+A plain run does only what the headline needs: set-up, --warmup and settle steps, the --steps timed steps, --dump-outputs, the JSON line.
+`--full` adds the side legs below (each still has its --no-* switch).  Besides the contract fields the line then carries
   roofline      -- the step's dominant kernel symbol (the whole-stack kernel `mlp_split_k` / `mlp_fwd_k`: forward
                    stack + backward data chain; per-layer `gemm_k` for wide encoders) timed with HIP events inside
                    training steps: ISSUED bf16 flops (6 x algorithmic) / time vs the 2.5 PFLOP/s dense bf16 peak, with
@@ -26,6 +27,7 @@ Besides the contract fields the JSON line carries
   ranks         -- N > 1: per rank the world size it saw and the wall time of each collective of the step
   cpu_baseline  -- oracle/torch_port.py (the reference's op sequence in PyTorch CPU ops) timed on
                    this box's host cores, rank 0 at N=1 only
+and loss_kernel(_pool_49152), dropin, split_bf16x3, dry_ranks_8 and secondary (see main()).
 """
 import argparse
 import json
@@ -54,6 +56,9 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the side legs (roofline, kernels, loss_kernel, cpu_baseline, dropin, native_fp32, "
+                         "split_bf16x3, dry_ranks_8, secondary; ranks at N > 1); a plain run measures the headline alone")
     ap.add_argument("--windows", type=int, default=1,
                     help="split the --steps timed steps into this many consecutive windows; the median window's time per step is reported")
     ap.add_argument("--n", "--latent-dim", dest="n", type=int, default=10)
@@ -457,9 +462,9 @@ def measure_traffic(args, kernel_symbol, timeout_s=150, child_args=None, grid_si
     if exe is None:
         return None, "rocprofv3 not on PATH"
     here = os.path.dirname(os.path.abspath(__file__))
-    child = [sys.executable, os.path.join(here, "bench.py"), "--steps", "6", "--warmup", "2", "--windows", "1", "--no-cpu-baseline", "--no-roofline",
-             "--no-native-leg", "--no-dropin", "--no-secondary", "--no-traffic", "--no-dry-leg", "--n", str(args.n), "--batch-size", str(args.batch_size),
-             "--p", str(args.p), "--space-type", args.space_type] + (["--native-fp32"] if args.native_fp32 else [])
+    # a plain run (no --full): the headline step alone
+    child = [sys.executable, os.path.join(here, "bench.py"), "--steps", "6", "--warmup", "2", "--windows", "1", "--n", str(args.n),
+             "--batch-size", str(args.batch_size), "--p", str(args.p), "--space-type", args.space_type] + (["--native-fp32"] if args.native_fp32 else [])
     if child_args is not None:      # another leg's command (bench.py --config c5 ...)
         child = [sys.executable, os.path.join(here, "bench.py")] + list(child_args)
     want = kernel_symbol.split(" (+")[0].split(" [")[0]
@@ -1170,85 +1175,86 @@ def main():
                         "native fp32 MFMA per-layer kernels for the forward and the data gradients (a width beyond 512); weight gradients of the "
                         "MFMA-sized layers in the split-bf16 arithmetic on plane copies made by clica_mlp_planes_from_f32") if wide_split else
                        "native fp32 MFMA" + ("" if tr.fused_forward else " (per-layer kernels: a width beyond 512)")))
-    if world > 1:
-        comm = comm_leg(tr, rank, world, device)
-        if rank == 0:
-            out["ranks"] = comm
-    if rank == 0 and not args.no_roofline:
-        roof, rows = roofline_leg(tr)
-        if world == 1 and not args.no_traffic:
-            tb_, src_ = measure_traffic(args, roof["kernel"])
-            if tb_ is not None:
-                roof["traffic_committed_profile"] = roof.get("traffic")
-                roof["traffic"], roof["traffic_source"] = tb_, src_
-            else:
-                roof["traffic_source"] = (roof.get("traffic_source") or "") + f" [in-run measurement unavailable: {src_}]"
-        out["roofline"] = roof
-        out["kernels"] = [{k: (round(v, 3) if isinstance(v, float) else v) for k, v in r.items()} for r in rows]
-        ll = loss_leg(tr)
-        out["loss_kernel"] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in ll.items()}
-        if world == 1 and (args.n, args.space_type, args.p) == (10, "box", 2):
-            # the same sweeps at the negatives pool of the 8-GPU job (49 152 rows: what bounds weak scaling)
-            tr8 = build_trainer(args, device, 1, emulate_pool_ranks=8)
-            for _ in range(3):
-                tr8.step()
-            torch.cuda.synchronize()
-            l8 = loss_leg(tr8, reps=10)
-            out["loss_kernel_pool_49152"] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in l8.items()}
-            del tr8
+    if args.full:      # the side legs; a plain run stops at the headline
+        if world > 1:
+            comm = comm_leg(tr, rank, world, device)
+            if rank == 0:
+                out["ranks"] = comm
+        if rank == 0 and not args.no_roofline:
+            roof, rows = roofline_leg(tr)
+            if world == 1 and not args.no_traffic:
+                tb_, src_ = measure_traffic(args, roof["kernel"])
+                if tb_ is not None:
+                    roof["traffic_committed_profile"] = roof.get("traffic")
+                    roof["traffic"], roof["traffic_source"] = tb_, src_
+                else:
+                    roof["traffic_source"] = (roof.get("traffic_source") or "") + f" [in-run measurement unavailable: {src_}]"
+            out["roofline"] = roof
+            out["kernels"] = [{k: (round(v, 3) if isinstance(v, float) else v) for k, v in r.items()} for r in rows]
+            ll = loss_leg(tr)
+            out["loss_kernel"] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in ll.items()}
+            if world == 1 and (args.n, args.space_type, args.p) == (10, "box", 2):
+                # the same sweeps at the negatives pool of the 8-GPU job (49 152 rows: what bounds weak scaling)
+                tr8 = build_trainer(args, device, 1, emulate_pool_ranks=8)
+                for _ in range(3):
+                    tr8.step()
+                torch.cuda.synchronize()
+                l8 = loss_leg(tr8, reps=10)
+                out["loss_kernel_pool_49152"] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in l8.items()}
+                del tr8
+                torch.cuda.empty_cache()
+        if world > 1:
+            dist.barrier()
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            from oracle.torch_port import time_reference_step      # checker/baseline leg only
+            threads = torch.get_num_threads()
+            med, _ = time_reference_step(n=args.n, B=args.batch_size, p=args.p, steps=5, warmup=2)
+            out["cpu_baseline"] = {"value": 1.0 / med, "unit": "steps/s", "cores": threads, "kind": "port",
+                                   "sample": f"5 timed + 2 warm-up full steps at B={args.batch_size}, n={args.n} (median), "
+                                             f"torch {torch.__version__} CPU ops, {os.cpu_count()} host cores visible"}
+            out["speedup_vs_cpu"] = out["value"] / out["cpu_baseline"]["value"]
+        if rank == 0 and world == 1 and not args.no_dropin:
+            out["dropin"] = dropin_leg(args, device)
+        if rank == 0 and world == 1 and split and not args.no_native_leg:
+            # the same step on the native fp32-MFMA kernels: its own value, its own roofline entry (fp32 flops / fp32 matrix peak)
+            del tr
             torch.cuda.empty_cache()
-    if world > 1:
-        dist.barrier()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        from oracle.torch_port import time_reference_step      # checker/baseline leg only
-        threads = torch.get_num_threads()
-        med, _ = time_reference_step(n=args.n, B=args.batch_size, p=args.p, steps=5, warmup=2)
-        out["cpu_baseline"] = {"value": 1.0 / med, "unit": "steps/s", "cores": threads, "kind": "port",
-                               "sample": f"5 timed + 2 warm-up full steps at B={args.batch_size}, n={args.n} (median), "
-                                         f"torch {torch.__version__} CPU ops, {os.cpu_count()} host cores visible"}
-        out["speedup_vs_cpu"] = out["value"] / out["cpu_baseline"]["value"]
-    if rank == 0 and world == 1 and not args.no_dropin:
-        out["dropin"] = dropin_leg(args, device)
-    if rank == 0 and world == 1 and split and not args.no_native_leg:
-        # the same step on the native fp32-MFMA kernels: its own value, its own roofline entry (fp32 flops / fp32 matrix peak)
-        del tr
-        torch.cuda.empty_cache()
-        tr2 = build_trainer(args, device, world, split_bf16=False)
-        capture_or_eager(tr2, args, rank, world, device)
-        w2, _ = timed_windows(tr2, min(args.steps, 200), args.warmup, 3, world, device)
-        el = float(np.median(w2)); nst = min(args.steps, 200)
-        leg = {"value": nst / el, "unit": "steps/s", "ms_per_step": 1e3 * el / nst, "steps": nst, "windows": len(w2), "dtype": "f32",
-               "final_loss": float(tr2.loss_out[3 * tr2.B].item()),
-               "what": "identical step, encoder GEMMs on v_mfma_f32_16x16x4_f32 / 32x32x2_f32 (split_bf16=False / CLICA_SPLIT_BF16=0)"}
-        if not args.no_roofline:
-            roof2, _ = roofline_leg(tr2, reps=10)
-            leg["roofline"] = {k: roof2[k] for k in ("kernel", "achieved", "peak", "unit", "frac", "avg_launch_us", "launches_per_step",
-                                                     "algorithmic_gflop_per_launch", "dtype")}
-        out["native_fp32"] = leg
-    if rank == 0 and world == 1 and not args.no_native_leg and getattr(args, "_f16_headline", False):
-        # the round-3 / round-4 arithmetic (bf16x3: six bf16 products, 6 B/element planes) next to the f16x2 headline, same box, same call
-        tr3 = build_trainer(args, device, world, split_arith="bf16")
-        capture_or_eager(tr3, args, rank, world, device)
-        w3, _ = timed_windows(tr3, min(args.steps, 200), args.warmup, 3, world, device)
-        el = float(np.median(w3)); nst = min(args.steps, 200)
-        out["split_bf16x3"] = {"value": nst / el, "unit": "steps/s", "ms_per_step": 1e3 * el / nst, "steps": nst, "windows": len(w3),
-                               "final_loss": float(tr3.loss_out[3 * tr3.B].item()),
-                               "what": "identical step in the bf16x3 split arithmetic (CLICA_SPLIT_ARITH=bf16: the headline arithmetic of rounds 3-4)"}
-        del tr3
-        torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_dry_leg and (args.n, args.space_type, args.p) == (10, "box", 2):
-        out["dry_ranks_8"] = dry_ranks_leg(args, device, R=8)
-        torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_secondary and (args.n, args.space_type, args.p) == (10, "box", 2):
-        out["secondary"] = secondary_leg(args, device)
-        if not args.no_conv_configs:
-            out["secondary"]["c4_3dident_resnet18"] = conv_config_leg("c4", device)
+            tr2 = build_trainer(args, device, world, split_bf16=False)
+            capture_or_eager(tr2, args, rank, world, device)
+            w2, _ = timed_windows(tr2, min(args.steps, 200), args.warmup, 3, world, device)
+            el = float(np.median(w2)); nst = min(args.steps, 200)
+            leg = {"value": nst / el, "unit": "steps/s", "ms_per_step": 1e3 * el / nst, "steps": nst, "windows": len(w2), "dtype": "f32",
+                   "final_loss": float(tr2.loss_out[3 * tr2.B].item()),
+                   "what": "identical step, encoder GEMMs on v_mfma_f32_16x16x4_f32 / 32x32x2_f32 (split_bf16=False / CLICA_SPLIT_BF16=0)"}
+            if not args.no_roofline:
+                roof2, _ = roofline_leg(tr2, reps=10)
+                leg["roofline"] = {k: roof2[k] for k in ("kernel", "achieved", "peak", "unit", "frac", "avg_launch_us", "launches_per_step",
+                                                         "algorithmic_gflop_per_launch", "dtype")}
+            out["native_fp32"] = leg
+        if rank == 0 and world == 1 and not args.no_native_leg and getattr(args, "_f16_headline", False):
+            # the round-3 / round-4 arithmetic (bf16x3: six bf16 products, 6 B/element planes) next to the f16x2 headline, same box, same call
+            tr3 = build_trainer(args, device, world, split_arith="bf16")
+            capture_or_eager(tr3, args, rank, world, device)
+            w3, _ = timed_windows(tr3, min(args.steps, 200), args.warmup, 3, world, device)
+            el = float(np.median(w3)); nst = min(args.steps, 200)
+            out["split_bf16x3"] = {"value": nst / el, "unit": "steps/s", "ms_per_step": 1e3 * el / nst, "steps": nst, "windows": len(w3),
+                                   "final_loss": float(tr3.loss_out[3 * tr3.B].item()),
+                                   "what": "identical step in the bf16x3 split arithmetic (CLICA_SPLIT_ARITH=bf16: the headline arithmetic of rounds 3-4)"}
+            del tr3
             torch.cuda.empty_cache()
-            out["secondary"]["c5_kitti_masks"] = conv_config_leg("c5", device)
-            try:
-                out["secondary"]["c5_kitti_masks"]["roofline"] = c5_conv_roofline(device, traffic=not args.no_traffic)
-            except Exception as e:      # noqa: BLE001
-                out["secondary"]["c5_kitti_masks"]["roofline"] = {"error": f"{type(e).__name__}: {e}"}
+        if rank == 0 and world == 1 and not args.no_dry_leg and (args.n, args.space_type, args.p) == (10, "box", 2):
+            out["dry_ranks_8"] = dry_ranks_leg(args, device, R=8)
+            torch.cuda.empty_cache()
+        if rank == 0 and world == 1 and not args.no_secondary and (args.n, args.space_type, args.p) == (10, "box", 2):
+            out["secondary"] = secondary_leg(args, device)
+            if not args.no_conv_configs:
+                out["secondary"]["c4_3dident_resnet18"] = conv_config_leg("c4", device)
+                torch.cuda.empty_cache()
+                out["secondary"]["c5_kitti_masks"] = conv_config_leg("c5", device)
+                try:
+                    out["secondary"]["c5_kitti_masks"]["roofline"] = c5_conv_roofline(device, traffic=not args.no_traffic)
+                except Exception as e:      # noqa: BLE001
+                    out["secondary"]["c5_kitti_masks"]["roofline"] = {"error": f"{type(e).__name__}: {e}"}
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

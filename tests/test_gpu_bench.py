@@ -1,4 +1,5 @@
-"""bench.py end to end on the GPU (short run): the contract JSON line with its roofline / kernels / loss legs and the native-fp32 leg."""
+"""bench.py end to end on the GPU (short runs): the contract JSON line of a plain run, and with --full its roofline / kernels / loss legs and the
+native-fp32 leg."""
 import json
 import os
 import subprocess
@@ -11,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_emits_contract_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -38,6 +39,27 @@ def test_bench_emits_contract_line():
     assert abs(line["final_loss"]) < 20 and abs(nat["final_loss"]) < 20
 
 
+def test_bench_plain_run_measures_the_headline_alone():
+    """Without --full the run sets up, warms up, times its steps and prints the contract line, nothing else: no side leg in the line, and
+    at most 30 s of the process's wall time outside its --warmup and --steps steps (import, set-up, capture, settle steps, exit)."""
+    import time
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "50", "--warmup", "5"],
+                       capture_output=True, text=True, timeout=300)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "final_loss"):
+        assert k in line, k
+    assert line["metric"] == "training steps/sec (B=6144, n=10 MLP)" and line["unit"] == "steps/s" and line["higher_is_better"] is True
+    assert line["steps"] == 50 and line["warmup"] == 5 and line["value"] > 100 and "f16x2 split" in line["dtype"]
+    for k in ("roofline", "kernels", "loss_kernel", "loss_kernel_pool_49152", "cpu_baseline", "speedup_vs_cpu", "dropin", "native_fp32",
+              "split_bf16x3", "dry_ranks_8", "secondary", "ranks"):
+        assert k not in line, k
+    outside = wall - (50 + 5) * line["ms_per_step"] * 1e-3
+    assert outside < 30.0, outside
+
+
 def test_bench_gpus_2_starts_its_own_ranks_and_falls_back_to_eager():
     """`python bench.py --gpus 2 ...` exactly as the driver types it for N = 1 (no torchrun, no WORLD_SIZE): bench.py starts the two
     ranks itself.  On this one-GPU box both ranks share cuda:0 and the collectives run over gloo (RCCL refuses two ranks on one
@@ -47,7 +69,7 @@ def test_bench_gpus_2_starts_its_own_ranks_and_falls_back_to_eager():
     env = dict(os.environ, CLICA_DIST_BACKEND="gloo", CLICA_BENCH_INJECT_CAPTURE_FAILURE="all", PYTHONFAULTHANDLER="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--windows", "2"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--windows", "2", "--full"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     assert "eager launches" in r.stderr

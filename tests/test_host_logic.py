@@ -588,6 +588,23 @@ def test_bench_self_launch_two_ranks():
     assert r.returncode != 0 and "WORLD_SIZE=1" in r.stderr
 
 
+def test_bench_side_legs_are_opt_in():
+    """`bench.py --gpus 1 --steps K --warmup W` measures the headline alone; the side legs (roofline, CPU baseline, other arithmetics and
+    configs, ...) run only under `--full`, where each keeps its --no-* switch."""
+    import sys
+    import bench
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "1"]
+        a = bench.parse()
+        assert a.full is False and (a.gpus, a.steps, a.warmup) == (1, 4, 1)
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline"]
+        a = bench.parse()
+        assert a.full is True and a.no_cpu_baseline is True
+    finally:
+        sys.argv = argv
+
+
 def test_lazy_roll_of_a_deferred_output_on_cpu():
     """`torch.roll(z1_rec, 1, 0)` of a deferred encoder output (the reference's z3_rec, main_mlp.py:272) is itself deferred: a LazyRoll
     that remembers its source (LpSimCLRLoss recognises it and never computes it) and gives every other consumer the real rolled tensor,

@@ -2,7 +2,7 @@
 # A/B of the config-3 leg (bench.py `secondary`): generic vs specialised f16x2 epilogue of gemm_split_k (clica_set_tuning "gemm16_epilogue").
 # usage (GPU box): bash tools/c3_ab.sh  ->  gpurun_out/c3_ab_{generic,specialised}.json
 mkdir -p gpurun_out
-FLAGS="--steps 100 --warmup 10 --windows 3 --no-conv-configs --no-native-leg --no-dropin --no-dry-leg --no-traffic --no-cpu-baseline"
+FLAGS="--steps 100 --warmup 10 --windows 3 --full --no-conv-configs --no-native-leg --no-dropin --no-dry-leg --no-traffic --no-cpu-baseline"
 for mode in 0 1; do
   name=$([ $mode = 0 ] && echo generic || echo specialised)
   python - $FLAGS > gpurun_out/c3_ab_$name.json 2> gpurun_out/c3_ab_$name.err <<PY

@@ -2,7 +2,7 @@
 # A/B of the config-3 leg (bench.py `secondary`) between library variants: bash tools/c3_lib_ab.sh <outdir> default <tag> ...   (REPS=n)
 out=$1; shift
 mkdir -p $out
-FLAGS="--steps 100 --warmup 10 --windows 3 --no-conv-configs --no-native-leg --no-dropin --no-dry-leg --no-traffic --no-cpu-baseline"
+FLAGS="--steps 100 --warmup 10 --windows 3 --full --no-conv-configs --no-native-leg --no-dropin --no-dry-leg --no-traffic --no-cpu-baseline"
 for rep in $(seq 1 ${REPS:-2}); do
 for tag in "$@"; do
   if [ "$tag" = "default" ]; then unset CLICA_LIB; else export CLICA_LIB=$PWD/cl_ica_amd/lib/libclica_hip_$tag.so; fi

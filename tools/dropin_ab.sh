@@ -3,7 +3,7 @@
 #   bash tools/dropin_ab.sh <key> [outdir]      (REPS=n)
 key=$1; out=${2:-gpurun_out/dropin_ab_$1}
 mkdir -p $out
-FLAGS="--steps 100 --warmup 10 --windows 1 --no-cpu-baseline --no-native-leg --no-secondary --no-traffic --no-dry-leg --no-roofline"
+FLAGS="--steps 100 --warmup 10 --windows 1 --full --no-cpu-baseline --no-native-leg --no-secondary --no-traffic --no-dry-leg --no-roofline"
 for rep in $(seq 1 ${REPS:-2}); do
 for mode in 0 1; do
   python - $FLAGS > $out/bench_${mode}_$rep.json 2> $out/err_$mode.txt <<PY

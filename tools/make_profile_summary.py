@@ -33,7 +33,7 @@ for name in ("pmc_fetch", "pmc_write", "pmc_sq", "pmc_lds", "pmc_valu", "pmc_l2"
             pm.setdefault(k, {}).update(v)
 stats = list(csv.DictReader(open(f"{src}/trace/t_kernel_stats.csv")))
 bench = json.load(open(f"{src}/bench_under_rocprof.json"))
-lines = [f"# Profile {tag}: `rocprofv3 --kernel-trace --stats -- python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-native-leg --no-dropin`", "",
+lines = [f"# Profile {tag}: `rocprofv3 --kernel-trace --stats -- python bench.py --steps 100 --warmup 10 --full --no-cpu-baseline --no-native-leg --no-dropin`", "",
          f"bench line under the profiler: {bench['value']:.1f} steps/s, {bench['ms_per_step']:.3f} ms/step ({bench['dtype']}); roofline entry: "
          f"`{bench['roofline']['kernel']}` {bench['roofline']['achieved']} TFLOP/s ({bench['roofline']['frac']:.3f} of {bench['roofline']['peak']}), "
          f"avg {bench['roofline']['avg_launch_us']} us/launch (device time stamps around the launches inside the replayed step graph, bench.py roofline leg).", "",

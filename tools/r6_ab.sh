@@ -6,7 +6,7 @@ mkdir -p $out
 for rep in $(seq 1 ${REPS:-2}); do
 for tag in "$@"; do
   if [ "$tag" = "default" ]; then unset CLICA_LIB; else export CLICA_LIB=$PWD/cl_ica_amd/lib/libclica_hip_$tag.so; fi
-  python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-dropin --no-native-leg --no-secondary --no-traffic --no-dry-leg 2>$out/err_$tag.txt | tail -1 > $out/bench_${tag}_$rep.json
+  python bench.py --steps 200 --warmup 20 --full --no-cpu-baseline --no-dropin --no-native-leg --no-secondary --no-traffic --no-dry-leg 2>$out/err_$tag.txt | tail -1 > $out/bench_${tag}_$rep.json
   python - "$tag" $out/bench_${tag}_$rep.json <<'PY'
 import json, sys
 try:

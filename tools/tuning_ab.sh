@@ -2,7 +2,7 @@
 # A/B of the headline step with one clica_set_tuning key off / on (two runs each, interleaved): bash tools/tuning_ab.sh <key> [outdir]
 key=$1; out=${2:-gpurun_out/ab_$1}
 mkdir -p $out
-FLAGS="--steps 200 --warmup 20 --no-cpu-baseline --no-dropin --no-native-leg --no-secondary --no-traffic --no-dry-leg"
+FLAGS="--steps 200 --warmup 20 --full --no-cpu-baseline --no-dropin --no-native-leg --no-secondary --no-traffic --no-dry-leg"
 for rep in 1 2; do
 for mode in 0 1; do
   python - $FLAGS > $out/bench_${mode}_$rep.json 2> $out/err_$mode.txt <<PY
