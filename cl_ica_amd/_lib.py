@@ -93,6 +93,11 @@ SIGNATURES: Dict[str, list] = {
     "clica_dot_loss_workspace_bytes": [C.POINTER(DotLossDesc), C.POINTER(c_size), C.POINTER(c_size)],
     "clica_dot_loss_fwd": [C.POINTER(DotLossDesc)] + _LOSS_FWD,
     "clica_dot_loss_bwd": [C.POINTER(DotLossDesc)] + _LOSS_BWD,
+    "clica_dot_loss_train_workspace_bytes": [C.POINTER(DotLossDesc), C.POINTER(c_size)],
+    "clica_dot_loss_fwd_train": [C.POINTER(DotLossDesc), c_f32p, c_i64, c_f32p, c_i64, c_f32p, c_i64, c_f32p, c_f32p, c_f32p,
+                                 c_f32p, c_i64, c_f32p, c_i64, C.c_void_p, c_size, C.c_void_p],
+    "clica_dot_loss_bwd_sym_train": [C.POINTER(DotLossDesc), c_f32p, c_i64, c_f32p, c_i64, c_f32p, c_f32p, c_f32p, c_i64, c_f32p, C.c_void_p,
+                                     C.c_void_p, c_size, C.c_void_p],
     "clica_linear_fwd": [c_f32p, c_i64, c_f32p, c_i64, c_f32p, c_f32p, c_i64, c_i64, c_i64, c_i64, c_i32, C.c_float, C.c_void_p],
     "clica_linear_dgrad": [c_f32p, c_i64, c_f32p, c_i64, c_f32p, c_i64, C.c_float, c_f32p, c_i64, c_i64, c_i64, c_i64, C.c_void_p],
     "clica_linear_wgrad_workspace_bytes": [c_i64, c_i64, c_i64, C.POINTER(c_size)],

@@ -100,8 +100,9 @@ class ContrastiveTrainer:
         self.dry_ranks = int(dry_ranks) if (self.world == 1 and self.dp) else 1
         if int(dry_ranks) > 1 and self.dry_ranks == 1:
             raise ValueError("dry_ranks needs an initialised one-rank process group and force_collectives=True")
-        if self.p == 0:
-            raise NotImplementedError("p=0 (SimCLRLoss) runs through cl_ica_amd.losses.SimCLRLoss, not the fused engine")
+        # p = 0: SimCLRLoss(normalize=False, tau, alpha) -- InfoNCE on dot products (losses.py:162-202), the objective of the
+        # reference's hypersphere experiment; the loss runs on the dot kind's training pair (csrc/dot_train.hip)
+        self.dot = self.p == 0
 
         mods = list(self.f)
         self.linears: List[nn.Linear] = [m for m in mods if isinstance(m, nn.Linear)]
@@ -323,7 +324,8 @@ class ContrastiveTrainer:
             self.dpre = torch.empty((R, n), **f32)
 
     def _allocate_loss(self, R):
-        """Buffers of the objective: the Lp-InfoNCE loss of the pair (outputs, workspaces, the negatives pool under data parallelism)."""
+        """Buffers of the objective: the InfoNCE loss of the pair -- Lp distances for p >= 1, dot products for p = 0 (the dot kind's
+        training pair) -- with its outputs, its workspace and the negatives pool under data parallelism."""
         dev, B, n = self.device, self.B, self.n
         f32 = dict(dtype=torch.float32, device=dev)
         self.dy = torch.empty((R, n), **f32)
@@ -332,6 +334,17 @@ class ContrastiveTrainer:
         pooled = self.dp or self.emulate_pool > 1
         self.z_all = torch.empty((Bg, n), **f32) if pooled else None
         self.lse_all = torch.empty((Bg,), **f32) if pooled else None
+        if self.dot:
+            # dot-product InfoNCE: one training pair (forward with its tile finisher, symmetric backward + reduction); its workspace
+            # holds arrival counters that must start at zero
+            self.desc = _lib.DotLossDesc(B=B, B3=Bg, n=n, tau=self.tau, alpha=self.alpha, normalize=0)
+            tb = C.c_size_t()
+            _lib.check(_lib.load().clica_dot_loss_train_workspace_bytes(C.byref(self.desc), C.byref(tb)), "dot train workspace")
+            self.loss_ws = torch.zeros(tb.value, dtype=torch.uint8, device=dev)
+            self.loss_train = True
+            self.early_tick = True
+            self._ticked = False
+            return
         self.desc = _lib.LpLossDesc(B=B, B3=Bg, n=n, p=self.p, tau=self.tau, alpha=self.alpha, compat=1, pow=1)
         fb, bb = C.c_size_t(), C.c_size_t()
         _lib.check(_lib.load().clica_lp_loss_workspace_bytes(C.byref(self.desc), C.byref(fb), C.byref(bb)), "workspace")
@@ -500,6 +513,9 @@ class ContrastiveTrainer:
             pool = self.z_all
         else:
             pool = y1
+        if self.dot:
+            self._dot_forward_backward(y1, y2, pool, lse, emu, dry)
+            return
         if self.loss_train:
             # forward + coefficient step (finalize), then -- after the all-gather of the row statistics under DP -- pair sweep +
             # reduction (+ the forward's means): 5 launches instead of 8
@@ -550,6 +566,30 @@ class ContrastiveTrainer:
                                              lse.data_ptr(), pool_lse.data_ptr(), None, None, None,
                                              self.dy[:B].data_ptr(), n, self.dy[B:].data_ptr(), n,
                                              self.loss_ws.data_ptr(), self.loss_ws.numel(), st), "clica_lp_loss_bwd_sym")
+
+    def _dot_forward_backward(self, y1, y2, pool, lse, emu, dry):
+        """p = 0: the dot kind's training pair.  Forward (one launch: pair sweep + tile finisher; writes loss_i, pos_i, lse_i and the
+        positive-pair part of dy), the all-gather of the row log-sum-exps under data parallelism, then the symmetric sweep and the
+        reduction launch that adds it into dy[:B], writes the three means and advances the step counter."""
+        lib, st = _lib.load(), _lib.stream_ptr()
+        B, n, o = self.B, self.n, self.loss_out
+        _lib.check(lib.clica_dot_loss_fwd_train(C.byref(self.desc), y1.data_ptr(), n, y2.data_ptr(), n, pool.data_ptr(), n,
+                                                o[:B].data_ptr(), o[B:2 * B].data_ptr(), lse.data_ptr(),
+                                                self.dy[:B].data_ptr(), n, self.dy[B:].data_ptr(), n,
+                                                self.loss_ws.data_ptr(), self.loss_ws.numel(), st), "clica_dot_loss_fwd_train")
+        if self.dp:
+            dist.all_gather_into_tensor(self.lse_all[:B * self.world] if dry else self.lse_all, lse, group=self.pg)
+            if dry:
+                self.lse_all.view(self.dry_ranks, B)[1:].copy_(self.lse_all[:B].unsqueeze(0))
+        elif emu:
+            self.lse_all.view(self.emulate_pool, B).copy_(lse.unsqueeze(0))
+        pool_lse = self.lse_all if (self.dp or emu) else lse
+        self._dy_parts = None
+        _lib.check(lib.clica_dot_loss_bwd_sym_train(C.byref(self.desc), y1.data_ptr(), n, pool.data_ptr(), n,
+                                                    lse.data_ptr(), pool_lse.data_ptr(), self.dy[:B].data_ptr(), n, o[3 * B:].data_ptr(),
+                                                    self.step_dev.data_ptr() if self.early_tick else None,
+                                                    self.loss_ws.data_ptr(), self.loss_ws.numel(), st), "clica_dot_loss_bwd_sym_train")
+        self._ticked = self.early_tick
 
     # Test hooks (class attributes, tests/test_gpu_engine.py): both the folded and the unfolded launch structures are product paths -- the
     # unfolded ones run under data parallelism and behind a head -- and the equivalence tests compare them on ONE trainer configuration.
@@ -1011,7 +1051,7 @@ class ContrastiveTrainer:
         """M = log2(e)/tau max_i |y_i - y_0|^2 of the largest embedding cloud the p = 2 matrix-core loss sweeps have seen in this
         trainer (0 on the VALU sweeps): their logit error scales with it (include/clica.h).  Host read + sync -- for
         log points, not for the step."""
-        if not self.loss_train:
+        if not self.loss_train or self.dot:        # (p = 0: the dot sweeps need no spread guard)
             return 0.0
         v = C.c_float(0.0)
         _lib.check(_lib.load().clica_lp_loss_train_spread(C.byref(self.desc), self.loss_ws.data_ptr(), self.loss_ws.numel(), C.byref(v),
@@ -1022,7 +1062,7 @@ class ContrastiveTrainer:
         """State of the device-side guard of the p = 2 matrix-core loss sweeps (include/clica.h, "THE GUARD"): the largest spread M seen, the
         last step's M, the limit in force and how many steps fell back to the coordinate-difference sweeps.  The decision itself is made
         per step by the kernels (also inside graph replays); this is a host read + sync for log points."""
-        if not self.loss_train:
+        if not self.loss_train or self.dot:        # (p = 0: the logits need no guard)
             return dict(max_spread=0.0, last_spread=0.0, limit=0.0, fallback_steps=0)
         v = (C.c_float * 4)()
         _lib.check(_lib.load().clica_lp_loss_train_guard(C.byref(self.desc), self.loss_ws.data_ptr(), self.loss_ws.numel(), v,
@@ -1049,7 +1089,7 @@ class ContrastiveTrainer:
             for lo, hi in (self.buckets.buckets if self.buckets is not None else []):
                 coll.append(dict(op="all_reduce", what="gradient arena [%d, %d)" % (lo, hi), bytes=4 * (hi - lo)))
         return dict(world=self.world, dry_ranks=self.dry_ranks, planned_ranks=ranks, batch_per_rank=B, pool_rows=int(self.desc.B3),
-                    loss_workspace_bytes=int(self.loss_ws.numel()), loss_entry_points="train pair" if self.loss_train else "generic",
+                    loss_workspace_bytes=int(self.loss_ws.numel()), loss_entry_points=("dot train pair" if self.dot else "train pair") if self.loss_train else "generic",
                     wgrad_halves=bool(self.wgrad_halves), wgrad_group_workspace_bytes=int(self.group_ws.numel()) if self.group_ws is not None else 0,
                     gradient_buckets=[list(b) for b in (self.buckets.buckets if self.buckets is not None else [])],
                     gradient_arena_elements=int(self.grad_arena.numel()), grad_scale=1.0 / ranks, collectives_per_step=coll,

@@ -6,7 +6,7 @@ unsupervised), same log lines and checkpoints (g.pth, sup_f.pth, unsup_f.pth).
     python -m torch.distributed.run --nproc-per-node 8 -m cl_ica_amd.train_mlp ...      # data parallel
 
 The unsupervised phase (the hot path) runs on ``ContrastiveTrainer``: on-device sampling, fused fp32-MFMA
-encoder, tiled Lp-InfoNCE, fused Adam, replayed from a HIP graph on one GPU; with several ranks each GPU
+encoder, tiled Lp-InfoNCE (p = 0: dot-product InfoNCE), fused Adam, replayed from a HIP graph on one GPU; with several ranks each GPU
 trains on its own batch against the all-gathered negatives pool.  On one GPU the supervised phase runs on
 ``SupervisedTrainer``: the same step with the MSE objective on the B rows of z1.
 """
@@ -117,8 +117,8 @@ def evaluate(h, latent_space, n_samples=4096):
 def autograd_train_step(h, loss, optimizer, z1, z2, supervised: bool, world: int = 1):
     """The reference's ``train_step`` verbatim in structure (main_mlp.py:258-285) on the drop-in modules, for the phases the
     fused engine does not cover: the SUPERVISED phase (``test = True``: ``F.mse_loss(z1_rec, z1)``, :274-276 -- the first of the
-    default ``test_list = [True, False]``) under data parallelism and p = 0 (SimCLRLoss).  Returns the 0-dim loss tensor (no host
-    sync)."""
+    default ``test_list = [True, False]``) under data parallelism.  Also the reference baseline the p = 0 (SimCLRLoss) engine step is
+    measured against (tools/simclr_engine_bench.py).  Returns the 0-dim loss tensor (no host sync)."""
     optimizer.zero_grad()
     z1_rec, z2_rec = h(z1), h(z2)
     # negatives = all z1_rec of the (global) batch: roll on one rank, autograd-aware all-gather on several
@@ -187,7 +187,7 @@ def _main(argv=None):
         h = lambda z: f(g(z))   # noqa: E731
         if total_loss_values is None or not args.resume_training:
             total_loss_values, lin_scores, perm_scores = [], [], []
-        fused = (world == 1) if supervised else args.p != 0
+        fused = (world == 1) if supervised else True
         contrastive_engine = fused and not supervised
         if fused and supervised:
             trainer = SupervisedTrainer(f, g.weight_stack(), spec, batch_size=args.batch_size, lr=args.lr, g_slope=g.slope,
@@ -201,7 +201,7 @@ def _main(argv=None):
             if world == 1 and not args.no_graph:
                 trainer.capture()
         else:
-            # supervised phase under data parallelism / p == 0: autograd over the drop-in modules; flat-arena HIP Adam whose gradient
+            # supervised phase under data parallelism: autograd over the drop-in modules; flat-arena HIP Adam whose gradient
             # arena is all-reduced under data parallelism (its 1/world average is applied inside the Adam launch)
             if world > 1:
                 for prm in f.parameters():
@@ -277,7 +277,8 @@ def _main(argv=None):
         engine_state = dict(arith=st.get("arith"), f16_flags=st.get("flags"), f16_steps_withheld=ga["skipped"], loss_max_spread=gs["max_spread"],
                             loss_spread_limit=gs["limit"], loss_fallback_steps=gs["fallback_steps"])
         log(f"engine: encoder arithmetic {st.get('arith')}" + (f", scale flags {st.get('flags')}, steps withheld by the guard {ga['skipped']}" if "flags" in st else "") +
-            f"; p = 2 loss guard: largest spread M = {gs['max_spread']:.0f} (limit {gs['limit']:.0f}), {gs['fallback_steps']} calls on the difference sweeps")
+            ("" if args.p == 0 else
+             f"; p = 2 loss guard: largest spread M = {gs['max_spread']:.0f} (limit {gs['limit']:.0f}), {gs['fallback_steps']} calls on the difference sweeps"))
     log("linear mean: {} std: {}".format(np.mean(final_lin), np.std(final_lin)))
     log("perm mean: {} std: {}".format(np.mean(final_perm), np.std(final_perm)))
     if world > 1:

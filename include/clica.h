@@ -249,6 +249,31 @@ int clica_dot_loss_bwd(const clica_dot_loss_desc* d,
                        float* dz1, int64_t ldd1, float* dz2, int64_t ldd2,
                        float* dz3, int64_t ldd3, int32_t accumulate_dz3,
                        void* workspace, size_t workspace_bytes, clica_stream_t stream);
+/* Training-step pair of the dot kind (what the fused engine calls at p = 0; csrc/dot_train.hip): the mathematics of clica_dot_loss_fwd +
+ * clica_dot_loss_bwd with z3 = `pool`, normalize = 0 and the default upstream gradient d(mean loss) = 1.
+ *   s_ij = <z1_i, pool_j>/tau, pos_i = <z1_i, z2_i>, lse_i = logsumexp([s_i., pos_i/tau]), loss_i = 2(alpha(-pos_i/tau) + (1-alpha) lse_i)
+ * REQUIREMENT: `pool` [B3,n] CONTAINS the B rows of z1 (the training step's pool: z1 itself, in place of the reference's roll(z1_rec),
+ * or the all-gather of every rank's z1) and every pool row is an anchor of the same objective (B3 >= B).
+ * fwd_train is ONE launch: a pair sweep with a true running maximum per row (no assumption on the row norms) whose last workgroup per
+ * 64-row tile finishes the tile's rows -- loss_i, pos_i (= -pos/tau, as clica_dot_loss_fwd), lse_i (log2 units, as clica_dot_loss_fwd),
+ * the positive-pair part of dz1 / dz2 (dz1 = c_i z2_i, dz2 = c_i z1_i, c_i = (2/B)((1-alpha) exp(pos_i/tau - lse_i) - alpha)/tau; either
+ * may be NULL) and the tile's sums of the three means.  bwd_sym_train is one symmetric sweep (s is symmetric:
+ * dz1_k += (2(1-alpha)/(B tau)) sum_j (w_kj + w_jk) pool_j, w_jk = exp(s_jk - lse_j) with lse_j from `pool_lse`, the all-gather of
+ * lse_i) -- no column pass, no dz3: under data parallelism it is the gradient of the SUM of all ranks' mean losses -- and a reduction
+ * launch that ADDS it into dz1, writes means[3] = {mean loss_i, mean(-pos_i/tau), mean lse_i} and advances *tick_counter (NULL: none).
+ * Both calls share ONE workspace of clica_dot_loss_train_workspace_bytes, ZERO-FILLED before its first use (arrival counters; every
+ * launch leaves them zero), untouched in between.  Rows of 1..64 coordinates; deterministic (fixed merge orders). */
+int clica_dot_loss_train_workspace_bytes(const clica_dot_loss_desc* d, size_t* bytes);
+int clica_dot_loss_fwd_train(const clica_dot_loss_desc* d,
+                             const float* z1, int64_t ld1, const float* z2, int64_t ld2, const float* pool, int64_t ldp,
+                             float* loss_i, float* pos_i, float* lse_i,
+                             float* dz1, int64_t ldd1, float* dz2, int64_t ldd2,
+                             void* workspace, size_t workspace_bytes, clica_stream_t stream);
+int clica_dot_loss_bwd_sym_train(const clica_dot_loss_desc* d,
+                                 const float* z1, int64_t ld1, const float* pool, int64_t ldp,
+                                 const float* lse_i, const float* pool_lse,
+                                 float* dz1, int64_t ldd1, float* means, int32_t* tick_counter /* NULL, or a device counter to advance by 1 */,
+                                 void* workspace, size_t workspace_bytes, clica_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Fused Linear (+bias) (+LeakyReLU)  --  the nn.Sequential get_mlp builds,
