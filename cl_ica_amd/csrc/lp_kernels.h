@@ -61,7 +61,10 @@ struct Params {
   float xs;       // logit = xs * neg * kscale : -1 for Lp distances, +1 for the dot-product kind
   int pow;        // 1: use sum |e|^p ; 0: its 1/p-th root
   int n;          // true embedding dim (<= NP)
-  // training entry points only (clica_lp_loss_fwd_train / bwd_sym_train: the pool CONTAINS the owner rows, integer p, pow):
+  // training entry points (clica_lp_loss_fwd_train / bwd_sym_train: the pool CONTAINS the owner rows).  The two forms below exist for
+  // p in {1, 2, 3} with pow on rows of <= 64 coordinates (fwd_partial_k<ZMAX> / bwd_pairs_k<FOLD>); the launchers (lp_loss_pk.hip) send
+  // every other form those entry points accept -- non-integer p >= 1, the root form pow = 0, wide rows -- through the running-maximum /
+  // two-exponential sweeps whatever the bits say, and `pre` / `gfold` stay 1 there:
   //   bit 0: forward without the running maximum -- logits of an Lp distance are <= 0 and the owner's own pool row gives exactly 0, so
   //          sum_j 2^x_ij >= 1 needs no rescaling (per pair: multiply, exp, add instead of max / subtract / exp / rescale)
   //   bit 1: backward coefficient with ONE exponential, 2^x (u_i + u_j) with u = C 2^-L per row (L = log2 of a sum >= 1, so 2^-L is in

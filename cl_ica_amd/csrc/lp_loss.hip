@@ -600,6 +600,7 @@ static int bwd_sym_train_impl(const clica_lp_loss_desc* d,
   if (rc) return rc;
   CLICA_CHECK_ARG(z1 && pool && lse_i && pool_lse && (dz1 || parts) && means && workspace, "clica_lp_loss_bwd_sym_train: NULL pointer");
   CLICA_CHECK_ARG(d->p >= 1.f && d->B3 >= d->B, "clica_lp_loss_bwd_sym_train: needs p >= 1 and a pool that contains the local rows");
+  CLICA_CHECK_ARG(ld1 >= d->n && ldp >= d->n && (!dz1 || ldd1 >= d->n), "clica_lp_loss_bwd_sym_train: leading dimension < n");
   const int64_t rows = d->B, cols = d->B3;
   Plan PF = make_plan(rows, cols, d->n, false), PR = make_plan(rows, cols, d->n, true);
   TrainWs w = carve_train(workspace, PF, PR, rows, cols, train_mfma(d));

@@ -22,7 +22,7 @@
 // (relative error <= 2^-18 per pair, unbiased), against three exact pieces of the pool features (u_j p'_j rounded once to fp32, then split
 // exactly): five products.  The W sums come out of the same product (ones / u columns), so the e_ij that weigh a'_i and p'_j are the same
 // numbers and the self pair cancels exactly.  Parity is measured, not assumed: tests/test_gpu_loss.py compares these sweeps with the fp64
-// oracle at the bench sizes and over spreads up to M = 15 000; CLICA_LP_MFMA=0 (or CLICA_LP_TRAIN_FAST without bit 2) keeps the VALU sweeps.
+// oracle at the bench sizes and over spreads up to M = 15 000; CLICA_LP_MFMA=0 keeps the VALU sweeps.
 //
 // Layout.  A prep launch writes the planes once per step, already in MFMA operand order, so staging is a linear copy and an operand is
 // one 16-byte LDS read:  row planes [tile of 32 rows][piece][k half][row] x 8 bf16 (operand of the logit product, for the anchors and

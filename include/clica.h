@@ -143,8 +143,13 @@ int clica_lp_loss_bwd_sym(const clica_lp_loss_desc* d,
  * REQUIREMENT (round 4): `pool` must CONTAIN the B rows of z1 bit for bit (it does in the training step: the pool is z1 itself or the
  * all-gather of every rank's z1).  The sweeps use it: every logit is <= 0 and the row's own pool entry gives exactly 0, so the forward
  * sums 2^x without a running maximum and the backward folds the row statistics into one factor per row (one exponential per pair).
- * For negatives that do not include the anchors use clica_lp_loss_fwd / clica_lp_loss_bwd.  CLICA_LP_TRAIN_FAST=0 restores the
- * general-purpose sweeps behind these entry points (A/B switch).
+ * For negatives that do not include the anchors use clica_lp_loss_fwd / clica_lp_loss_bwd.  (These forms are compiled in: there is no
+ * run-time switch back to the general-purpose sweeps.)
+ * FORMS: every p >= 1 (p < 1 is rejected: its eps branch is not symmetric), pow = 1 and pow = 0, compat on and off, any tau > 0 and alpha,
+ * n = 1..512, any B <= B3, leading dimensions >= n (smaller ones are rejected by both calls).  The fixed-maximum / folded sweeps serve
+ * p in {1, 2, 3} with pow = 1 on rows of <= 64 coordinates; a non-integer p, the root form (pow = 0: the gradient of the root at the
+ * zero-distance self pair is masked to 0, as torch.norm's backward does) and wide rows take the running-maximum / two-exponential sweeps
+ * behind the same entry points.  All of them are held to 1e-5 against the fp64 oracle by tests/test_gpu_train_pairs.py.
  * p = 2, pow, n <= 10 (BASELINE config 2: main_mlp.py defaults): the two pair sweeps run on the bf16 matrix cores (csrc/lp_mfma.hip:
  * logit = one augmented inner product of bf16 pieces, gradient = a second product against the pool) and z1 / pool must additionally be
  * UNCHANGED between the two calls (fwd_train leaves their operand planes in the workspace).  The expansion |a|^2 + |b|^2 - 2ab behind

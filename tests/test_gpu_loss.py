@@ -536,7 +536,7 @@ def matrix_cores_every_pool():
     _lib.check(_lib.load().clica_lp_loss_set_matrix_cores(-1), "default policy")
 
 
-def _train_pair(z1, z2, pool, pool_lse, n, p, tau, alpha, compat=1):
+def _train_pair(z1, z2, pool, pool_lse, n, p, tau, alpha, compat=1, pow=1):
     """clica_lp_loss_fwd_train + clica_lp_loss_bwd_sym_train on device tensors; returns (out [3B+3], dz [2B, n], path).
     The matrix-core sweeps build their planes on the grid the PREVIOUS call measured (csrc/lp_mfma.h), so a fresh workspace gets one
     un-checked forward call first; `path` is 1 only if the checked forward then really ran on the matrix cores (no fallback counted)."""
@@ -544,7 +544,7 @@ def _train_pair(z1, z2, pool, pool_lse, n, p, tau, alpha, compat=1):
     from cl_ica_amd import _lib
     lib = _lib.load()
     B, B3 = z1.shape[0], pool.shape[0]
-    d = _lib.LpLossDesc(B=B, B3=B3, n=n, p=float(p), tau=tau, alpha=alpha, compat=compat, pow=1)
+    d = _lib.LpLossDesc(B=B, B3=B3, n=n, p=float(p), tau=tau, alpha=alpha, compat=compat, pow=pow)
     nb, path = C.c_size_t(), C.c_int32()
     _lib.check(lib.clica_lp_loss_train_workspace_bytes(C.byref(d), C.byref(nb)), "ws")
     _lib.check(lib.clica_lp_loss_train_path(C.byref(d), C.byref(path)), "path")
