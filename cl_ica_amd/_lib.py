@@ -90,6 +90,9 @@ SIGNATURES: Dict[str, list] = {
                                           C.c_void_p, c_size, C.POINTER(DyParts), C.c_void_p],
     "clica_mse_loss_workspace_bytes": [c_i64, c_i32, C.POINTER(c_size)],
     "clica_mse_loss_fwd_bwd": [c_f32p, c_i64, c_f32p, c_i64, c_i64, c_i32, c_f32p, c_i64, c_f32p, C.c_void_p, C.c_void_p, c_size, C.c_void_p],
+    "clica_r2_loss_workspace_bytes": [c_i64, c_i32, C.POINTER(c_size)],
+    "clica_r2_loss_fwd": [c_f32p, c_i64, c_f32p, c_i64, c_i64, c_i32, c_i32, c_i32, c_f32p, c_f32p, c_f32p, C.c_void_p, c_size, C.c_void_p],
+    "clica_r2_loss_bwd": [c_f32p, c_i64, c_f32p, c_i64, c_i64, c_i32, c_i32, c_i32, c_f32p, c_f32p, c_f32p, c_i64, C.c_void_p],
     "clica_dot_loss_workspace_bytes": [C.POINTER(DotLossDesc), C.POINTER(c_size), C.POINTER(c_size)],
     "clica_dot_loss_fwd": [C.POINTER(DotLossDesc)] + _LOSS_FWD,
     "clica_dot_loss_bwd": [C.POINTER(DotLossDesc)] + _LOSS_BWD,

@@ -18,10 +18,10 @@ from typing import Optional
 
 import torch
 
-from . import _lib, lazy
+from . import _lib, lazy, ops
 
 __all__ = ["CLLoss", "ConditionalPairCLLoss", "MarginalPairCLLoss", "LpSimCLRLoss", "SimCLRLoss", "UniformityLoss", "AlignmentLoss",
-           "AlignmentUniformityLoss"]
+           "AlignmentUniformityLoss", "R2Loss"]
 
 
 class CLLoss(ABC):
@@ -452,3 +452,51 @@ class AlignmentUniformityLoss(CLLoss):
         u, u_i, _ = self._unif.loss(z1_rec, z3_rec)
         per_item = (1.0 - self.alpha) * a_i + self.alpha * u_i if a_i.shape == u_i.shape else None
         return (1.0 - self.alpha) * a + self.alpha * u, per_item, [a, u]
+
+
+class _R2LossFn(torch.autograd.Function):
+    """autograd bridge to clica_r2_loss_fwd / clica_r2_loss_bwd: one launch each, nothing fetched to the host."""
+
+    @staticmethod
+    def forward(ctx, y_pred, y, reduction, mode):
+        (a, _), (b, _) = _prep("y_pred", y_pred), _prep("y", y)
+        if a.shape != b.shape:
+            raise ValueError(f"shape mismatch: y_pred {tuple(a.shape)}, y {tuple(b.shape)}")
+        out, _, inv_var = ops.r2_loss_fwd(a, b, reduction, mode)
+        ctx.save_for_backward(a, b, inv_var)
+        ctx.reduction, ctx.mode = reduction, mode
+        return out if reduction == "none" else out.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        a, b, inv_var = ctx.saved_tensors
+        if ctx.reduction == "none":
+            g = g.detach().to(torch.float32).contiguous()          # (a sum over the columns hands an expanded scalar back)
+        else:
+            g = _scal(g).reshape(1)
+        return ops.r2_loss_bwd(a, b, inv_var, g, ctx.reduction, ctx.mode), None, None, None
+
+
+class R2Loss:
+    """(Negative) R2 score (reference losses.py:480-503): per column ``1 - mean((y_pred - y)^2, 0) / var(y, 0, unbiased=False)``,
+    reduced over the columns by ``reduction`` ("mean", "sum", anything else: none) and negated unless ``mode == "r2"``.  Forward and
+    backward are one HIP launch each (clica_r2_loss_fwd / _bwd); the gradient flows to ``y_pred`` only."""
+
+    def __init__(self, reduction="none", mode="negative_r2"):
+        assert mode in ("negative_r2", "r2")
+
+        self.mode = mode
+        self.reduction = reduction
+
+    def forward(self, y_pred, y):
+        y_pred, y = lazy.plain(y_pred), lazy.plain(y)
+        if y.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("R2Loss differentiates with respect to y_pred only: the target y requires grad (detach it; no "
+                                      "caller of the reference differentiates the target)")
+        reduction = self.reduction if self.reduction in ("mean", "sum") else "none"       # losses.py:492-495
+        return _R2LossFn.apply(y_pred, y, reduction, self.mode)
+
+    def __call__(self, *args, **kwargs):
+        return self.forward(*args, **kwargs)

@@ -728,6 +728,83 @@ def mse_loss_fwd_bwd(y: torch.Tensor, target: torch.Tensor, dy: Optional[torch.T
     return loss_out, dy
 
 
+# ------------------------------------------------------------------------------- R2 objective
+R2_REDUCTIONS = {"none": 0, "mean": 1, "sum": 2}       # CLICA_R2_REDUCE_*
+R2_MODES = {"r2": 0, "negative_r2": 1}                 # CLICA_R2_MODE_*
+
+# zeroed workspaces of clica_r2_loss_fwd per (device, M, n).  An entry is never replaced or freed (a few KB each), so a captured graph
+# that recorded its pointer stays valid whatever runs afterwards; one entry serves one launch at a time (one stream per shape).
+_R2_WS = {}
+
+
+def r2_loss_workspace(M: int, n: int, device) -> torch.Tensor:
+    """The cached zeroed workspace of clica_r2_loss_fwd for M x n on `device` (its arrival counter must start at zero)."""
+    device = torch.device(device)
+    key = (device.index if device.index is not None else torch.cuda.current_device(), int(M), int(n))
+    ws = _R2_WS.get(key)
+    if ws is None:
+        nb = C.c_size_t()
+        check(load().clica_r2_loss_workspace_bytes(int(M), int(n), C.byref(nb)), "clica_r2_loss_workspace_bytes")
+        if torch.cuda.is_current_stream_capturing():
+            # (memory allocated while capturing belongs to the graph's pool and its zeroing would be replayed: not something to cache)
+            raise ClicaError(f"r2_loss: no workspace for shape ({M}, {n}) yet -- run the step once eagerly before capturing it")
+        ws = _R2_WS[key] = torch.zeros(nb.value, dtype=torch.uint8, device=device)
+    _lib.note_graph_use(ws)
+    return ws
+
+
+def _r2_codes(reduction: str, mode: str) -> Tuple[int, int]:
+    if reduction not in R2_REDUCTIONS:
+        raise ValueError(f"reduction {reduction!r} (one of {sorted(R2_REDUCTIONS)})")
+    if mode not in R2_MODES:
+        raise ValueError(f"mode {mode!r} (one of {sorted(R2_MODES)})")
+    return R2_REDUCTIONS[reduction], R2_MODES[mode]
+
+
+def r2_loss_fwd(y_pred: torch.Tensor, y: torch.Tensor, reduction: str = "mean", mode: str = "negative_r2",
+                out: Optional[torch.Tensor] = None, r2_cols: Optional[torch.Tensor] = None, inv_var: Optional[torch.Tensor] = None,
+                ws: Optional[torch.Tensor] = None):
+    """(Negative) R2 score per column of y_pred against the target y (reference losses.py:489-500) in one deterministic launch
+    (clica_r2_loss_fwd).  Strided row views pass without a copy.  Returns (out: [n] for "none" else [1], r2_cols [n], inv_var [n]);
+    inv_var is what r2_loss_bwd needs."""
+    red, md = _r2_codes(reduction, mode)
+    (y_pred, ldp), (y, ldy) = _mat("y_pred", y_pred), _mat("y", y)
+    if y.shape != y_pred.shape:
+        raise ValueError(f"target {tuple(y.shape)} does not match y_pred {tuple(y_pred.shape)}")
+    M, n = y_pred.shape
+    dev = y_pred.device
+    out = torch.empty(n if red == 0 else 1, dtype=torch.float32, device=dev) if out is None else out
+    r2_cols = torch.empty(n, dtype=torch.float32, device=dev) if r2_cols is None else r2_cols
+    inv_var = torch.empty(n, dtype=torch.float32, device=dev) if inv_var is None else inv_var
+    ws = r2_loss_workspace(M, n, dev) if ws is None else ws
+    check(load().clica_r2_loss_fwd(y_pred.data_ptr(), ldp, y.data_ptr(), ldy, M, n, red, md, out.data_ptr(), r2_cols.data_ptr(),
+                                   inv_var.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()), "clica_r2_loss_fwd")
+    return out, r2_cols, inv_var
+
+
+def r2_loss_bwd(y_pred: torch.Tensor, y: torch.Tensor, inv_var: torch.Tensor, g: torch.Tensor, reduction: str = "mean",
+                mode: str = "negative_r2", dy: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """d out / d y_pred of r2_loss_fwd times the upstream gradient g (a device tensor: n values for "none", else one) in one
+    element-wise launch (clica_r2_loss_bwd); inv_var is the forward's."""
+    red, md = _r2_codes(reduction, mode)
+    (y_pred, ldp), (y, ldy) = _mat("y_pred", y_pred), _mat("y", y)
+    if y.shape != y_pred.shape:
+        raise ValueError(f"target {tuple(y.shape)} does not match y_pred {tuple(y_pred.shape)}")
+    M, n = y_pred.shape
+    require_cuda(inv_var, "inv_var"); require_cuda(g, "g")
+    if inv_var.numel() != n or not inv_var.is_contiguous():
+        raise ValueError(f"inv_var must hold n = {n} contiguous values, got {tuple(inv_var.shape)}")
+    if g.numel() != (n if red == 0 else 1) or not g.is_contiguous():
+        raise ValueError(f"g must hold {n if red == 0 else 1} contiguous value(s) for reduction {reduction!r}, got {tuple(g.shape)}")
+    dy = torch.empty((M, n), dtype=torch.float32, device=y_pred.device) if dy is None else dy
+    (dyv, lddy) = _mat("dy", dy)
+    if dyv.data_ptr() != dy.data_ptr() or tuple(dy.shape) != (M, n):
+        raise ValueError(f"dy must be a row-major (strided) {M} x {n} view")
+    check(load().clica_r2_loss_bwd(y_pred.data_ptr(), ldp, y.data_ptr(), ldy, M, n, red, md, inv_var.data_ptr(), g.data_ptr(),
+                                   dy.data_ptr(), lddy, stream_ptr()), "clica_r2_loss_bwd")
+    return dy
+
+
 def tick(counter: torch.Tensor):
     check(load().clica_tick(counter.data_ptr(), stream_ptr()), "clica_tick")
 

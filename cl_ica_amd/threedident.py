@@ -8,6 +8,9 @@ What runs where (BASELINE.json configs[3]: "ResNet-18 encoder ... conv path via 
     (``clica_linear_*``), the rescaling layer (``clica_rescale_*`` / ``clica_softclip_*``), the losses on column slices
     ``z[:, :k]`` (strided views, no copies) and -- optionally -- Adam (``cl_ica_amd.optim.Adam``).
 
+Both halves of the driver are mirrored: ``make_unsupervised_loss`` / ``train_step`` (``train_unsupervised``) and
+``make_supervised_loss`` / ``train_step_supervised`` (``train_supervised``, the driver's default ``--mode``).
+
 ``setup_f`` reproduces the module layout of :365-371 (``nn.Sequential(backbone, LeakyReLU, Linear, rescaling)``), i.e.
 the reference's state-dict keys ``0.*`` (backbone), ``2.weight``, ``2.bias``, ``3.r`` / ``3.max_abs_bound``.
 """
@@ -18,10 +21,11 @@ from typing import Callable, Optional
 import torch
 from torch import nn
 
-from . import layers, lazy, losses
+from . import layers, lazy, losses, ops
 from .encoders import _MLPStackFn
 
-__all__ = ["setup_f", "make_unsupervised_loss", "train_step", "HipLinear", "unpack_item_list"]
+__all__ = ["setup_f", "make_unsupervised_loss", "train_step", "HipLinear", "unpack_item_list", "make_supervised_loss",
+           "train_step_supervised"]
 
 
 class HipLinear(nn.Linear):
@@ -129,3 +133,80 @@ def train_step(data, loss, optimizer, f, sync: bool = True):
     if not sync:
         return total_loss_value, total_loss_per_item_value, losses_value
     return total_loss_value.item(), total_loss_per_item_value, unpack_item_list(losses_value)
+
+
+class _MSELossFn(torch.autograd.Function):
+    """``F.mse_loss(y_pred, y)`` (mean over all elements) on clica_mse_loss_fwd_bwd: the loss and d loss / d y_pred come from ONE launch;
+    the backward only scales that gradient by the upstream scalar."""
+
+    @staticmethod
+    def forward(ctx, y_pred, y):
+        loss, dy = ops.mse_loss_fwd_bwd(y_pred.detach(), y.detach(), ws=_mse_workspace(y_pred.shape[0], y_pred.shape[1], y_pred.device))
+        ctx.save_for_backward(dy)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        (dy,) = ctx.saved_tensors
+        return dy * g, None
+
+
+_MSE_WS = {}      # (device, M, n) -> zeroed workspace, never replaced or freed (as ops.r2_loss_workspace: a captured graph keeps its pointer)
+
+
+def _mse_workspace(M: int, n: int, device) -> torch.Tensor:
+    key = (device.index if device.index is not None else torch.cuda.current_device(), int(M), int(n))
+    ws = _MSE_WS.get(key)
+    if ws is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"mse loss: no workspace for shape ({M}, {n}) yet -- run the step once eagerly before capturing it")
+        ws = _MSE_WS[key] = ops.mse_loss_workspace(M, n, device)
+    return ws
+
+
+class HipMSELoss:
+    """``torch.nn.MSELoss(reduction="mean")`` for 2-D fp32 device tensors; differentiates with respect to ``y_pred``."""
+
+    reduction = "mean"
+
+    def forward(self, y_pred, y):
+        y_pred, y = lazy.plain(y_pred), lazy.plain(y)
+        if y_pred.dim() != 2 or y.shape != y_pred.shape:
+            raise ValueError(f"shape mismatch: y_pred {tuple(y_pred.shape)}, y {tuple(y.shape)} (2-D, equal shapes)")
+        if y.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("the HIP MSE objective differentiates with respect to y_pred only: the target requires grad")
+        return _MSELossFn.apply(y_pred, y)
+
+    def __call__(self, *args, **kwargs):
+        return self.forward(*args, **kwargs)
+
+
+def make_supervised_loss(args):
+    """Loss selection of ``train_supervised`` (main_3dident.py:574-577): ``args.supervised_loss`` is "r2" (negative mean R2 score) or
+    "mse"; called as ``loss(hz1, z1)``."""
+    kind = getattr(args, "supervised_loss", "r2")
+    if kind == "r2":
+        return losses.R2Loss(reduction="mean", mode="negative_r2")
+    if kind == "mse":
+        return HipMSELoss()
+    raise ValueError(f"supervised_loss {kind!r}")
+
+
+def train_step_supervised(data, loss, optimizer, f, sync: bool = True):
+    """One supervised step (main_3dident.py:585-601): one encoder pass on the first view, the loss against its true latents,
+    backward, optimizer step.  Returns the loss as a python float like the reference when ``sync`` (one host sync), the device
+    scalar otherwise."""
+    (z1, _), (x1, _) = data
+    optimizer.zero_grad()
+    hz1 = lazy.plain(f(x1))
+    del x1
+    total_loss_value = loss(hz1, z1.to(hz1.device))
+    total_loss_value.backward()
+    if hasattr(optimizer, "all_reduce_grads"):
+        optimizer.all_reduce_grads()
+    optimizer.step()
+    if not sync:
+        return total_loss_value
+    return total_loss_value.item()

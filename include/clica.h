@@ -534,6 +534,29 @@ int clica_mlp_wgrad_split16_tail(int64_t M, int32_t n_layers, const void* const*
                                  int32_t accumulate, const void* state, const int32_t* a_index, const int32_t* d_index,
                                  int32_t tail_slabs, void* workspace, size_t workspace_bytes, clica_stream_t stream);
 
+/* (Negative) R2 score per latent column -- losses.R2Loss, reference losses.py:480-503, the supervised 3DIdent objective
+ * (main_3dident.py:575: reduction "mean", mode "negative_r2").  y_pred, y: [M][n] fp32, rows strided by ldp / ldy, 1 <= n <= 256:
+ *   var_j = mean_i (y_ij - mean_i y_ij)^2 (biased),  mse_j = mean_i (y_pred_ij - y_ij)^2,  r2_j = 1 - mse_j / var_j
+ *   out = s reduce(r2): s = +1 (CLICA_R2_MODE_R2) or -1 (CLICA_R2_MODE_NEGATIVE_R2); out has n elements for CLICA_R2_REDUCE_NONE, else 1
+ *   dY_ij = g_j s w (-2 / M) (y_pred_ij - y_ij) / var_j: w = 1 / n for the mean, else 1; g: n upstream gradients for NONE, else 1
+ * Forward, ONE launch: every wave leaves Welford / Chan moment partials (of y minus its first row) per column in the workspace, the last to arrive (an arrival
+ * counter in the workspace, put back to zero by the launch itself: graph replays need no reset) merges them in a fixed order and writes
+ * r2_cols[n], inv_var[n] = 1 / var_j and out.  No floating-point atomics: eager launches and replays give the same bits.  The variance is
+ * never formed as E[y^2] - E[y]^2, so it keeps fp32 accuracy when |mean| >> std.  A column without variance (constant, or M = 1) gets
+ * what IEEE division gives (-inf, +inf or nan), as in the reference; no other column is affected.  Backward, one element-wise launch:
+ * reads inv_var (the forward's) and g from device memory.  The workspace (clica_r2_loss_workspace_bytes, 16-byte aligned) is zeroed once
+ * before its first use; one workspace serves one launch at a time. */
+#define CLICA_R2_REDUCE_NONE 0
+#define CLICA_R2_REDUCE_MEAN 1
+#define CLICA_R2_REDUCE_SUM 2
+#define CLICA_R2_MODE_R2 0
+#define CLICA_R2_MODE_NEGATIVE_R2 1
+int clica_r2_loss_workspace_bytes(int64_t M, int32_t n, size_t* bytes);
+int clica_r2_loss_fwd(const float* y_pred, int64_t ldp, const float* y, int64_t ldy, int64_t M, int32_t n, int32_t reduction, int32_t mode,
+                      float* out, float* r2_cols, float* inv_var, void* workspace, size_t workspace_bytes, clica_stream_t stream);
+int clica_r2_loss_bwd(const float* y_pred, int64_t ldp, const float* y, int64_t ldy, int64_t M, int32_t n, int32_t reduction, int32_t mode,
+                      const float* inv_var, const float* g, float* dY, int64_t lddy, clica_stream_t stream);
+
 /* Weight gradients + optimizer in one call (round 5: the N = 1 training step has no optimizer launch of its own).  The reduction that
  * ends clica_mlp_wgrad_split / _split16 applies torch.optim.Adam's update (main_mlp.py:312, as clica_adam_step_at) to every element
  * it has just reduced; dW[l] (contiguous: lddw[l] = K[l]) and db[l] must be views of ONE gradient arena `grad` that this call covers
