@@ -47,31 +47,50 @@ __global__ __launch_bounds__(THREADS) void sample_k(Desc d, const float* __restr
   const int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x;
   if (i >= M) return;
   const uint32_t step = step_dev ? (uint32_t)step_dev[0] : 0u;
-  Philox g(d.seed, (uint32_t)i, step, d.stream_id);
+  Philox g(d.seed, (uint32_t)i, step, d.stream_id, ROW_BLOCK0);
   const int n = d.n;
   float* o = out + i * ldo;
   const float* mu = mean ? mean + i * ldm : nullptr;   // ldm == 0 broadcasts one row
 
   if (d.dist == CLICA_DIST_VMF) {
-    // Wood (1994) / Ulrich rejection for w = <x, mu>  (vmf.py:88-114), then a tangent direction (vmf.py:125-134)
+    // Wood (1994) / Ulrich rejection for w = <x, mu>  (vmf.py:88-114), then a tangent direction (vmf.py:125-134).
+    // Carried in 1 - b, 1 - x0, 1 - w and 1 + w: as kappa grows x0 and w crowd against 1, where 1 - x0 * x0, 1 - x0 * w and
+    // sqrt(1 - w * w) of the textbook form cancel in fp32 (1 - w below 3e-8 became an atom at x == mu: 2 % of the draws at
+    // n = 2, kappa = 1e4; the same at w = -1 for a small kappa).  The acceptance test kappa w + dim log(1 - x0 w) - c >= log u
+    // with c = kappa x0 + dim log(1 - x0^2) is kappa (w - x0) + dim log((1 - x0 w) / (1 - x0^2)) >= log u.
     const float dim = (float)(n - 1), kappa = d.scale;
-    const float b = dim / (sqrtf(4.f * kappa * kappa + dim * dim) + 2.f * kappa);
-    const float x0 = (1.f - b) / (1.f + b);
-    const float c = kappa * x0 + dim * logf(1.f - x0 * x0);
-    float w = 1.f;
+    const float rt = sqrtf(4.f * kappa * kappa + dim * dim);
+    const float b = dim / (rt + 2.f * kappa);
+    const float omb = (4.f * kappa * kappa / (rt + dim) + 2.f * kappa) / (rt + 2.f * kappa);   // 1 - b
+    const float x0 = omb / (1.f + b), omx = 2.f * b / (1.f + b);                                // x0, 1 - x0
+    const float inv = 1.f / (omx * (2.f - omx));                                                // 1 / (1 - x0^2)
+    float omw = 0.f, opw = 2.f;                                                                 // 1 - w, 1 + w
     for (int it = 0; it < 1000; ++it) {
-      const float g1 = g.gamma(0.5f * dim), g2 = g.gamma(0.5f * dim);
-      const float z = g1 / (g1 + g2);                       // Beta(d/2, d/2)
-      w = (1.f - (1.f + b) * z) / (1.f - (1.f - b) * z);
+      const float g1 = g.gamma(0.5f * dim), g2 = g.gamma(0.5f * dim);                           // z = g1 / (g1 + g2) ~ Beta(d/2, d/2)
+      const float den = 1.f / (g2 + b * g1);                // w = (1 - (1 + b) z) / (1 - (1 - b) z)
+      omw = 2.f * b * g1 * den; opw = 2.f * g2 * den;
       const float u = g.uniform_open();
-      if (kappa * w + dim * logf(1.f - x0 * w) - c >= logf(u)) break;
+      if (kappa * (omx - omw) + dim * logf((omx + x0 * omw) * inv) >= logf(u)) break;
     }
-    float dot = 0.f, mm = 0.f;
-    for (int k = 0; k < n; ++k) { const float v = g.normal(); o[k] = v; dot += v * mu[k]; mm += mu[k] * mu[k]; }
-    const float coef = dot / sqrtf(mm);                      // mu * <mu,v> / |mu|  (vmf.py:128-132)
+    const float w = omw < 1.f ? 1.f - omw : opw - 1.f;
     float ss = 0.f;
-    for (int k = 0; k < n; ++k) { const float t = o[k] - mu[k] * coef; o[k] = t; ss += t * t; }
-    const float sc = sqrtf(fmaxf(1.f - w * w, 0.f)) / sqrtf(ss);
+    for (int tries = 0; tries < 16; ++tries) {
+      float dot = 0.f, mm = 0.f, vv = 0.f;
+      for (int k = 0; k < n; ++k) { const float v = g.normal(); o[k] = v; dot += v * mu[k]; mm += mu[k] * mu[k]; vv += v * v; }
+      const float coef = dot / sqrtf(mm);                    // mu * <mu,v> / |mu|  (vmf.py:128-132)
+      float res = 0.f;
+      for (int k = 0; k < n; ++k) { const float t = o[k] - mu[k] * coef; o[k] = t; res += t * mu[k]; }
+      // second Gram-Schmidt pass: where v is nearly parallel to mu the difference above keeps a component along mu that is no longer
+      // small against what is left (n = 2: one row in 1e5 ended 1e-3 off unit norm)
+      const float fix = res / mm;
+      ss = 0.f;
+      for (int k = 0; k < n; ++k) { const float t = o[k] - mu[k] * fix; o[k] = t; ss += t * t; }
+      // a v within 1e-7 rad of +-mu leaves a tangent part that is rounding, or exactly zero (n = 2: a row or two in 1e8 came out
+      // 3e-2 off unit norm, or NaN after the division below): below 1e-5 rad v is drawn again.  The refused cap is symmetric about
+      // mu, the accepted tangent direction stays uniform.
+      if (ss > 1e-10f * vv) break;
+    }
+    const float sc = ss > 0.f ? sqrtf(omw * opw) / sqrtf(ss) : 0.f;   // sqrt(1 - w^2)
     for (int k = 0; k < n; ++k) o[k] = o[k] * sc + w * mu[k];
     return;
   }

@@ -1,20 +1,23 @@
 // Device side of the latent samplers that other translation units launch inside kernels of their own (sampler.hip holds the
 // kernels and the C ABI; fused_mlp.hip merges the pair draw into the weight-pack launch of the training step: mlp_pack2_sample_k).
 // Philox4x32-10, counter-based: (seed; element index, draw block, step, stream id) -> the same numbers whichever kernel hosts the draw.
+// The row-wise kernel (sphere, vMF) counts ROWS in the first word where the element-wise kernels count elements: its draw blocks start at
+// ROW_BLOCK0, so that row i of a sphere draw and element i of a box or R^n draw at the same seed, stream id and step share no numbers.
 #pragma once
 #include "common.h"
 
 namespace clica {
 namespace rng {
 constexpr int THREADS = 256;
+constexpr uint32_t ROW_BLOCK0 = 0x80000000u;   // (an element-wise draw uses a handful of blocks, 4096 truncation tries a few thousand)
 
 struct Philox {
   uint32_t key0, key1;
   uint32_t c0, c1, c2, c3;   // c0 = element index, c1 = draw block, c2 = step, c3 = stream id
   uint32_t o0, o1, o2, o3;   // named registers: a runtime-indexed array would live in scratch memory
   int have;
-  __device__ Philox(uint64_t seed, uint32_t idx, uint32_t step, uint32_t stream)
-      : key0((uint32_t)seed), key1((uint32_t)(seed >> 32)), c0(idx), c1(0), c2(step), c3(stream), have(0) {}
+  __device__ Philox(uint64_t seed, uint32_t idx, uint32_t step, uint32_t stream, uint32_t block0 = 0u)
+      : key0((uint32_t)seed), key1((uint32_t)(seed >> 32)), c0(idx), c1(block0), c2(step), c3(stream), have(0) {}
   __device__ void refill() {
     uint32_t a0 = c0, a1 = c1, a2 = c2, a3 = c3, k0 = key0, k1 = key1;
 #pragma unroll
