@@ -58,7 +58,20 @@ __global__ __launch_bounds__(THREADS) void rescale_bwd_k(const float* __restrict
   }
 }
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
+// e^t to about an ulp over the whole fp32 range.  Neither __expf nor expf gives that in this build: __expf rounds t log2(e) before the
+// exponent is split off, and under -ffp-contract=fast the compiler's own expansion of expf contracts its `hi - rint(hi)` into an fma that
+// already holds the low half of the product, which the expansion then adds a second time -- either way an error of ulp(|t| log2 e) in the
+// EXPONENT, 2.4e-6 / 1.8e-6 relative at t = -60, where sigmoid(t) = e^t is all the result there is.  Here every product-sum is an explicit
+// fmaf (nothing left to contract): t (c + cc) - rint(t c) in two roundings, v_exp_f32 on |a| <= 1/2, ldexp.  NaN stays NaN, +-inf and
+// overflow go to inf / 0 through the clamp on the integer part.  These kernels wait for memory, not for the ALU.
+__device__ __forceinline__ float exp_f32(float t) {
+  const float c = 0x1.715476p+0f, cc = 0x1.4ae0bep-26f;      // log2(e) = c + cc
+  const float e = fminf(fmaxf(rintf(t * c), -160.f), 160.f);
+  float a = fmaf(t, c, -e);
+  a = fmaf(t, cc, a);
+  return ldexpf(__builtin_amdgcn_exp2f(a), (int)e);
+}
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + exp_f32(-x)); }
 
 __global__ __launch_bounds__(THREADS) void softclip_fwd_k(const float* __restrict__ X, int64_t ldx, const float* __restrict__ bound,
                                                          float* __restrict__ Y, int64_t ldy, int64_t M, int n) {

@@ -783,6 +783,19 @@ int clica_moments(const float* A, int64_t lda, int32_t da, const float* B, int64
  * over one flat parameter arena.  `step_dev` is a device int32 holding the number of
  * updates already applied; the call uses t = *step_dev + 1 for the bias corrections and
  * leaves *step_dev unchanged (advance it with clica_tick so a graph replay stays valid).
+ *   m = beta1 m + (1 - beta1) g s ;  v = beta2 v + (1 - beta2) (g s)^2          (s = grad_scale)
+ *   p -= (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ * The betas arrive as fp32.  The complements are formed from those values in fp32
+ * (1.f - beta: exact for beta = 0 and beta >= 0.5), the bias corrections in fp64 from the
+ * same fp32 betas, pow((double)beta, t), and rounded once to fp32; every other operation is
+ * one correctly rounded fp32 operation (csrc/adam_math.h).  The update is therefore
+ * self-consistent and the PARAMETERS follow torch.optim.Adam's to fp32 rounding, but with
+ * beta2 = 0.999 the factor (1 - beta2) is 1.f - 0.999f = 0.00099998713 where torch multiplies
+ * a float32 state by float(1 - 0.999) = 0.0010000000475: exp_avg_sq is interchangeable with
+ * torch's float32 state to 1.3e-5 relative, not 1e-5 (exp_avg: 2.2e-7, the same effect at
+ * beta1 = 0.9); betas that are fp32 numbers (0.5, 0.875) have no such gap.  A property of an
+ * ABI that takes fp32 betas; tests/test_gpu_elementwise.py measures and bounds it.
+ * `count` > 0 elements; all four arenas 16-byte aligned, otherwise CLICA_E_INVALID.
  * ---------------------------------------------------------------------------------- */
 int clica_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t count,
                     float lr, float beta1, float beta2, float eps, float grad_scale,
