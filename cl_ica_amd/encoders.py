@@ -727,19 +727,94 @@ class FusedMLP(nn.Sequential):
         return compute(x)
 
 
+NORM_MODE = "hip"            # test / benchmark hook (tests/test_gpu_norm.py, tools/normed_mlp_bench.py): "torch" runs the normalisation modules' own forward
+
+
+class _BNLeakyFn(torch.autograd.Function):
+    """nn.BatchNorm1d in training mode + the LeakyReLU behind it (slope = 1: none) on clica_bn_lrelu_fwd_train / _bwd.  `mod` is the
+    module itself: its running statistics are updated in place by the forward's second launch, as the module's own forward does."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, mod, slope):
+        y, save_mean, save_invstd = ops.batchnorm_lrelu_fwd(x, weight, bias, mod.running_mean, mod.running_var, mod.eps, mod.momentum, slope)
+        ctx.save_for_backward(x, y, weight, save_mean, save_invstd)
+        ctx.slope = slope
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, y, weight, save_mean, save_invstd = ctx.saved_tensors
+        dx, dw, db = ops.batchnorm_lrelu_bwd(x, y, gy.contiguous(), weight, save_mean, save_invstd, ctx.slope)
+        return dx, dw, db, None, None
+
+
+class _GNLeakyFn(torch.autograd.Function):
+    """nn.GroupNorm(1, C) + the LeakyReLU behind it (slope = 1: none) on clica_gn_lrelu_fwd / _bwd."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps, slope):
+        y, mean, rstd = ops.groupnorm_lrelu_fwd(x, weight, bias, eps, slope)
+        ctx.save_for_backward(x, y, weight, mean, rstd)
+        ctx.slope = slope
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, y, weight, mean, rstd = ctx.saved_tensors
+        dx, dw, db = ops.groupnorm_lrelu_bwd(x, y, gy.contiguous(), weight, mean, rstd, ctx.slope)
+        return dx, dw, db, None, None
+
+
+def _norm_on_hip(m, x) -> bool:
+    """Do the norm kernels cover this module on this input?  Anything else runs the module's own forward, as before."""
+    if NORM_MODE != "hip" or not x.is_cuda or x.dtype != torch.float32:
+        return False
+    if isinstance(m, nn.BatchNorm1d):
+        if not (m.affine and m.track_running_stats and m.momentum is not None and x.shape[1] == m.num_features):
+            return False
+        ok = m.training or not torch.is_grad_enabled()           # inference inside autograd: the module's own forward
+    elif isinstance(m, nn.GroupNorm):
+        ok = m.num_groups == 1 and m.num_channels >= 2 and m.affine and x.shape[1] == m.num_channels
+    else:
+        return False
+    return ok and m.weight.is_cuda and m.weight.dtype == torch.float32      # (a mismatch is the module's own error to raise)
+
+
 class NormedMLP(nn.Sequential):
-    """get_mlp(layer_normalization="bn" | "gn"): same modules and state dict as the reference's Sequential; Linear and
-    LeakyReLU run on the HIP kernels (per layer), the normalisation modules are torch's."""
+    """get_mlp(layer_normalization="bn" | "gn"): same modules and state dict as the reference's Sequential; every Linear runs on the
+    HIP GEMM kernels (per layer), and a normalisation module with the LeakyReLU directly behind it is ONE call of the fused norm
+    kernels (csrc/norm.hip; a norm with nothing behind it: slope = 1).  The modules stay plain nn.BatchNorm1d / nn.GroupNorm objects;
+    configurations the kernels do not cover (`_norm_on_hip`) run the module's own forward and the stand-alone activation kernel."""
 
     def forward(self, x):
         x = lazy.plain(x)
         if x.dim() != 2:
             x = x.reshape(-1, x.shape[-1])
-        for m in self:
+        mods = list(self)
+        i = 0
+        while i < len(mods):
+            m = mods[i]
+            i += 1
             if isinstance(m, nn.Linear):
                 x = _MLPStackFn.apply(x, 0.01, m.weight, m.bias)       # one-layer stack: no activation
             elif isinstance(m, nn.LeakyReLU):
                 x = ls._LeakyFn.apply(x.contiguous(), float(m.negative_slope))
+            elif _norm_on_hip(m, x):
+                slope = 1.0
+                if i < len(mods) and isinstance(mods[i], nn.LeakyReLU) and mods[i].negative_slope >= 0:
+                    slope = float(mods[i].negative_slope)
+                    i += 1
+                x = x.contiguous()
+                if isinstance(m, nn.GroupNorm):
+                    x = _GNLeakyFn.apply(x, m.weight, m.bias, float(m.eps), slope)
+                elif m.training:
+                    if x.shape[0] == 1:
+                        raise ValueError(f"Expected more than 1 value per channel when training, got input size {x.shape}")
+                    ops.norm_workspace("bn", x.shape[0], x.shape[1], x.device)    # (raises while capturing without a warm-up: before anything is counted)
+                    m.num_batches_tracked.add_(1)                      # in place on the device: capturable
+                    x = _BNLeakyFn.apply(x, m.weight, m.bias, m, slope)
+                else:
+                    x = ops.batchnorm_lrelu_eval(x, m.weight, m.bias, m.running_mean, m.running_var, float(m.eps), slope)
             else:
                 x = m(x)
         return x
@@ -755,9 +830,9 @@ def get_mlp(n_in: int, n_out: int, layers: List[int], layer_normalization: Optio
         layers: number of neurons for each hidden layer (the reference appends ``n_out`` to the
             caller's list in place, encoders.py:56; reproduced)
         layer_normalization: None | "bn" | "gn" (encoders.py:41-44).  With a normalisation between the layers the
-            stack cannot run as one fused kernel: every Linear runs on the HIP GEMM kernels, the activation on the HIP
-            elementwise kernel, and BatchNorm1d / GroupNorm(1, .) are torch's own device modules (none of the reference's
-            drivers passes this argument, so it is outside the measured hot path)
+            stack cannot run as one fused kernel: every Linear runs on the HIP GEMM kernels, and BatchNorm1d /
+            GroupNorm(1, .) run fused with the LeakyReLU behind them on the HIP norm kernels (csrc/norm.hip; the modules
+            stay torch's own objects -- see NormedMLP; none of the reference's drivers passes this argument)
         output_normalization: None | "fixed_sphere" | "learnable_sphere" | "fixed_box" | "learnable_box"
         output_normalization_kwargs: forwarded to the head (e.g. ``init_r`` for the sphere)
     """

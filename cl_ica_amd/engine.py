@@ -105,6 +105,11 @@ class ContrastiveTrainer:
         self.dot = self.p == 0
 
         mods = list(self.f)
+        for idx, m in enumerate(mods):
+            # the fused step runs the Linear / LeakyReLU stack only: with a normalisation in between it would train another network
+            if isinstance(m, (nn.modules.batchnorm._BatchNorm, nn.GroupNorm, nn.LayerNorm)):
+                raise ValueError(f"{type(self).__name__}: the encoder holds a normalisation module ({idx}: {m}); the fused step runs plain "
+                                 "Linear / LeakyReLU stacks only -- train get_mlp(layer_normalization=...) through autograd")
         self.linears: List[nn.Linear] = [m for m in mods if isinstance(m, nn.Linear)]
         slopes = {m.negative_slope for m in mods if isinstance(m, nn.LeakyReLU)}
         self.slope = slopes.pop() if slopes else 0.01

@@ -805,6 +805,133 @@ def r2_loss_bwd(y_pred: torch.Tensor, y: torch.Tensor, inv_var: torch.Tensor, g:
     return dy
 
 
+# ------------------------------------------------------------------------------- BatchNorm1d / GroupNorm(1, C) + LeakyReLU
+NORM_KINDS = {"bn": 0, "gn": 1}                        # CLICA_NORM_BATCH / CLICA_NORM_GROUP
+
+# partial-sum workspaces of the norm kernels per (device, kind, M, C); as _R2_WS an entry is never replaced or freed, so a pointer a
+# captured graph recorded stays valid.  No initial contents are needed; one entry serves one launch at a time on one stream.
+_NORM_WS = {}
+
+
+def norm_workspace(kind: str, M: int, C_: int, device) -> torch.Tensor:
+    """The cached workspace of clica_bn_lrelu_fwd_train / _bwd ("bn") or clica_gn_lrelu_bwd ("gn") for M x C on `device`."""
+    if kind not in NORM_KINDS:
+        raise ValueError(f"kind {kind!r} (one of {sorted(NORM_KINDS)})")
+    device = torch.device(device)
+    key = (device.index if device.index is not None else torch.cuda.current_device(), kind, int(M), int(C_))
+    ws = _NORM_WS.get(key)
+    if ws is None:
+        nb = C.c_size_t()
+        check(load().clica_norm_workspace_bytes(NORM_KINDS[kind], int(M), int(C_), 1.0, C.byref(nb)), "clica_norm_workspace_bytes")
+        if torch.cuda.is_current_stream_capturing():
+            # (memory allocated while capturing belongs to the graph's pool: not something to cache)
+            raise ClicaError(f"norm: no {kind} workspace for shape ({M}, {C_}) yet -- run the step once eagerly before capturing it")
+        ws = _NORM_WS[key] = torch.empty(max(nb.value, 16), dtype=torch.uint8, device=device)
+    _lib.note_graph_use(ws)
+    return ws
+
+
+def _norm_mat(name: str, t: torch.Tensor) -> torch.Tensor:
+    require_cuda(t, name)
+    if t.dim() != 2 or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous [M, C] matrix, got shape {tuple(t.shape)} strides {t.stride()}")
+    return t
+
+
+def _norm_vec(name: str, t: torch.Tensor, n: int) -> torch.Tensor:
+    require_cuda(t, name)
+    if t.numel() != n or not t.is_contiguous():
+        raise ValueError(f"{name} must hold {n} contiguous values, got {tuple(t.shape)}")
+    return t
+
+
+def batchnorm_lrelu_fwd(x, weight, bias, running_mean=None, running_var=None, eps: float = 1e-5, momentum: float = 0.1,
+                        slope: float = 0.01):
+    """Training BatchNorm1d over the rows of x [M, C] (M >= 2) fused with LeakyReLU(slope) (slope = 1: none) in two launches
+    (clica_bn_lrelu_fwd_train); running_mean / running_var, when given, are updated in place as nn.BatchNorm1d does.
+    Returns (y, save_mean [C], save_invstd [C]); the last two are what batchnorm_lrelu_bwd needs."""
+    x = _norm_mat("x", x)
+    M, n = x.shape
+    _norm_vec("weight", weight, n); _norm_vec("bias", bias, n)
+    if (running_mean is None) != (running_var is None):
+        raise ValueError("running_mean and running_var come together")
+    if running_mean is not None:
+        _norm_vec("running_mean", running_mean, n); _norm_vec("running_var", running_var, n)
+    y = torch.empty_like(x)
+    save_mean = torch.empty(n, dtype=torch.float32, device=x.device)
+    save_invstd = torch.empty(n, dtype=torch.float32, device=x.device)
+    nb = C.c_size_t()        # (validates M, C and the slope before a workspace is looked up)
+    check(load().clica_norm_workspace_bytes(0, M, n, float(slope), C.byref(nb)), "clica_norm_workspace_bytes")
+    ws = norm_workspace("bn", M, n, x.device)
+    check(load().clica_bn_lrelu_fwd_train(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), M, n, float(eps), float(momentum), float(slope),
+                                          y.data_ptr(), save_mean.data_ptr(), save_invstd.data_ptr(), ptr(running_mean), ptr(running_var),
+                                          ws.data_ptr(), ws.numel(), stream_ptr()), "clica_bn_lrelu_fwd_train")
+    return y, save_mean, save_invstd
+
+
+def batchnorm_lrelu_eval(x, weight, bias, running_mean, running_var, eps: float = 1e-5, slope: float = 0.01):
+    """Inference BatchNorm1d on the running statistics fused with LeakyReLU(slope): one element-wise launch (clica_bn_lrelu_fwd_eval)."""
+    x = _norm_mat("x", x)
+    M, n = x.shape
+    for nm, t in (("weight", weight), ("bias", bias), ("running_mean", running_mean), ("running_var", running_var)):
+        _norm_vec(nm, t, n)
+    y = torch.empty_like(x)
+    check(load().clica_bn_lrelu_fwd_eval(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), running_mean.data_ptr(), running_var.data_ptr(),
+                                         M, n, float(eps), float(slope), y.data_ptr(), stream_ptr()), "clica_bn_lrelu_fwd_eval")
+    return y
+
+
+def batchnorm_lrelu_bwd(x, y, dy, weight, save_mean, save_invstd, slope: float = 0.01):
+    """(dx, dweight, dbias) of batchnorm_lrelu_fwd from its input x, its OUTPUT y (the gate) and the saved statistics: two launches
+    (clica_bn_lrelu_bwd)."""
+    x, y, dy = _norm_mat("x", x), _norm_mat("y", y), _norm_mat("dy", dy)
+    M, n = x.shape
+    if y.shape != x.shape or dy.shape != x.shape:
+        raise ValueError(f"x {tuple(x.shape)}, y {tuple(y.shape)} and dy {tuple(dy.shape)} must agree")
+    _norm_vec("weight", weight, n); _norm_vec("save_mean", save_mean, n); _norm_vec("save_invstd", save_invstd, n)
+    dx = torch.empty_like(x)
+    dw = torch.empty(n, dtype=torch.float32, device=x.device)
+    db = torch.empty(n, dtype=torch.float32, device=x.device)
+    ws = norm_workspace("bn", M, n, x.device)
+    check(load().clica_bn_lrelu_bwd(x.data_ptr(), y.data_ptr(), dy.data_ptr(), weight.data_ptr(), save_mean.data_ptr(),
+                                    save_invstd.data_ptr(), M, n, float(slope), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(),
+                                    ws.numel(), stream_ptr()), "clica_bn_lrelu_bwd")
+    return dx, dw, db
+
+
+def groupnorm_lrelu_fwd(x, weight, bias, eps: float = 1e-5, slope: float = 0.01):
+    """GroupNorm(1, C) over each row of x [M, C] fused with LeakyReLU(slope) in one launch (clica_gn_lrelu_fwd).
+    Returns (y, mean [M], rstd [M]); the last two are what groupnorm_lrelu_bwd needs."""
+    x = _norm_mat("x", x)
+    M, n = x.shape
+    _norm_vec("weight", weight, n); _norm_vec("bias", bias, n)
+    y = torch.empty_like(x)
+    mean = torch.empty(M, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(M, dtype=torch.float32, device=x.device)
+    check(load().clica_gn_lrelu_fwd(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), M, n, float(eps), float(slope), y.data_ptr(),
+                                    mean.data_ptr(), rstd.data_ptr(), stream_ptr()), "clica_gn_lrelu_fwd")
+    return y, mean, rstd
+
+
+def groupnorm_lrelu_bwd(x, y, dy, weight, mean, rstd, slope: float = 0.01):
+    """(dx, dweight, dbias) of groupnorm_lrelu_fwd: two launches (clica_gn_lrelu_bwd)."""
+    x, y, dy = _norm_mat("x", x), _norm_mat("y", y), _norm_mat("dy", dy)
+    M, n = x.shape
+    if y.shape != x.shape or dy.shape != x.shape:
+        raise ValueError(f"x {tuple(x.shape)}, y {tuple(y.shape)} and dy {tuple(dy.shape)} must agree")
+    _norm_vec("weight", weight, n); _norm_vec("mean", mean, M); _norm_vec("rstd", rstd, M)
+    dx = torch.empty_like(x)
+    dw = torch.empty(n, dtype=torch.float32, device=x.device)
+    db = torch.empty(n, dtype=torch.float32, device=x.device)
+    nb = C.c_size_t()
+    check(load().clica_norm_workspace_bytes(1, M, n, float(slope), C.byref(nb)), "clica_norm_workspace_bytes")
+    ws = norm_workspace("gn", M, n, x.device)
+    check(load().clica_gn_lrelu_bwd(x.data_ptr(), y.data_ptr(), dy.data_ptr(), weight.data_ptr(), mean.data_ptr(), rstd.data_ptr(), M, n,
+                                    float(slope), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()),
+          "clica_gn_lrelu_bwd")
+    return dx, dw, db
+
+
 def tick(counter: torch.Tensor):
     check(load().clica_tick(counter.data_ptr(), stream_ptr()), "clica_tick")
 

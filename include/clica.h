@@ -622,6 +622,39 @@ int clica_leaky_relu_fwd(const float* X, int64_t ldx, float* Y, int64_t ldy, int
 int clica_leaky_relu_bwd(const float* Yact, int64_t ldy, const float* dY, int64_t lddy, float* dX, int64_t lddx,
                          int64_t M, int32_t n, float slope, clica_stream_t stream);
 
+/* BatchNorm1d / GroupNorm(1, C) fused with the LeakyReLU behind them: the hidden-layer normalisations of
+ * get_mlp(layer_normalization = "bn" | "gn").  fp32, row-major CONTIGUOUS [M, C]:
+ *   Y = lrelu(Z, slope),  Z = gamma xhat + beta;  slope = 1: no activation follows, slope = 0: ReLU, slope < 0 is refused
+ *   (the backward takes its gate from the saved output Y: Y > 0 -> 1, else slope; Z is never recomputed).
+ * BatchNorm, training (M >= 2): xhat = (X - mean_c) invstd_c with the biased batch variance, invstd = 1 / sqrt(M2 / M + eps);
+ *   save_mean[C] / save_invstd[C] are what the backward needs; running_mean / running_var (NULL: do not track) become
+ *   (1 - momentum) running + momentum (mean | M2 / (M - 1)).  Two launches: Welford / Chan partials of X minus its first row per
+ *   (row split, column) into the workspace, then an apply launch in which every workgroup merges the partials of its columns in
+ *   split order.  The variance is never formed as E[x^2] - E[x]^2.  Backward, two launches of the same shape:
+ *   dX = gamma invstd (dZ - sum dZ / M - xhat sum(dZ xhat) / M), dgamma = sum dZ xhat, dbeta = sum dZ.
+ * BatchNorm, inference: one element-wise launch on the running statistics.
+ * GroupNorm(1, C): statistics per row (two-pass: mean, then sum (x - mean)^2), rstd = 1 / sqrt(var + eps); mean[M] / rstd[M] are what
+ *   the backward needs.  Forward one launch; backward two (dX and per-wave-slot partials of dgamma / dbeta, then their sum in slot order).
+ * No floating-point atomics, no in-kernel counters: eager launches and graph replays give the same bits.  The workspace
+ * (clica_norm_workspace_bytes, 16-byte aligned, no initial contents needed) serves one call at a time; the forward of
+ * GroupNorm needs none.  clica_norm_workspace_bytes is host-only and validates a configuration: -1 for M < 2 (batch), C < 1, slope < 0. */
+#define CLICA_NORM_BATCH 0
+#define CLICA_NORM_GROUP 1
+int clica_norm_workspace_bytes(int32_t kind, int64_t M, int32_t C, float slope, size_t* bytes);
+int clica_bn_lrelu_fwd_train(const float* X, const float* gamma, const float* beta, int64_t M, int32_t C, float eps, float momentum,
+                             float slope, float* Y, float* save_mean, float* save_invstd, float* running_mean /*[C] or NULL*/,
+                             float* running_var /*[C] or NULL*/, void* workspace, size_t workspace_bytes, clica_stream_t stream);
+int clica_bn_lrelu_fwd_eval(const float* X, const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                            int64_t M, int32_t C, float eps, float slope, float* Y, clica_stream_t stream);
+int clica_bn_lrelu_bwd(const float* X, const float* Y, const float* dY, const float* gamma, const float* save_mean,
+                       const float* save_invstd, int64_t M, int32_t C, float slope, float* dX, float* dgamma, float* dbeta,
+                       void* workspace, size_t workspace_bytes, clica_stream_t stream);
+int clica_gn_lrelu_fwd(const float* X, const float* gamma, const float* beta, int64_t M, int32_t C, float eps, float slope, float* Y,
+                       float* mean, float* rstd, clica_stream_t stream);
+int clica_gn_lrelu_bwd(const float* X, const float* Y, const float* dY, const float* gamma, const float* mean, const float* rstd,
+                       int64_t M, int32_t C, float slope, float* dX, float* dgamma, float* dbeta, void* workspace,
+                       size_t workspace_bytes, clica_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Convolution stack of the KITTI-masks encoder  --  BetaVAE_H, /root/reference/kitti_masks/model.py:41-56:
  * Conv2d(k = 4, stride 2, pad 1) + ReLU stages as implicit GEMMs (fp32 MFMA, csrc/linear.hip, conv section), channels-last.
