@@ -727,29 +727,37 @@ struct Pack3Args {
   PackSeg seg[MAXSEG];
 };
 __global__ __launch_bounds__(256) void mlp_pack3_k(Pack3Args a) {
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= a.first[a.nseg]) return;
+  // wave-uniform segment record through scalar loads, all eight weights requested before the first is used: see pack2_block
+  const unsigned wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), ln = threadIdx.x & 63u;
+  const int64_t idx_w = (int64_t)blockIdx.x * 256 + wv * 64u;
+  if (idx_w >= a.first[a.nseg]) return;
   int sidx = 0;
 #pragma unroll
-  for (int i = 1; i < MAXSEG; ++i) sidx += (i < a.nseg && idx >= a.first[i]) ? 1 : 0;
-  const PackSeg& sg = a.seg[sidx];
-  const unsigned d = (unsigned)(idx - a.first[sidx]);
+  for (int i = 1; i < MAXSEG; ++i) sidx += (i < a.nseg && idx_w >= a.first[i]) ? 1 : 0;
+  const PackSeg sg = a.seg[sidx];
+  u32x4* const dst_p = a.dst[sidx];
+  const int64_t ent = a.entries[sidx];
+  const unsigned frag = (unsigned)((idx_w - a.first[sidx]) >> 6);
+  const unsigned d = frag * 64u + ln;
   const unsigned kiters = (unsigned)(sg.cols + KI - 1) / KI;
-  const unsigned lane = d & 63u, frag = d >> 6;
   const unsigned cb = frag / kiters, ki = frag - cb * kiters;
-  const int n = (int)(cb * 16u + (lane & 15u)), k = (int)(ki * KI + 8u * (lane >> 4));
-  unsigned h[8], m[8], l[8];
+  const int n = (int)(cb * 16u + (ln & 15u)), k = (int)(ki * KI + 8u * (ln >> 4));
+  const int64_t sn = sg.transposed ? 1 : sg.ldw, sk = sg.transposed ? sg.ldw : 1;
+  float w[8];
 #pragma unroll
   for (int u = 0; u < 8; ++u) {
-    float v = 0.f;
-    if (n < sg.rows && k + u < sg.cols) v = sg.transposed ? sg.W[(int64_t)(k + u) * sg.ldw + n] : sg.W[(int64_t)n * sg.ldw + k + u];
-    split3(v, h[u], m[u], l[u]);
+    const bool ok = n < sg.rows && k + u < sg.cols;
+    const float x = sg.W[ok ? (int64_t)n * sn + (int64_t)(k + u) * sk : 0];
+    w[u] = ok ? x : 0.f;
   }
+  unsigned h[8], m[8], l[8];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) split3(w[u], h[u], m[u], l[u]);
   auto pk = [](const unsigned (&b)[8]) {
     return (u32x4){(b[0] >> 16) | b[1], (b[2] >> 16) | b[3], (b[4] >> 16) | b[5], (b[6] >> 16) | b[7]};
   };
-  u32x4* dst = a.dst[sidx] + d;
-  dst[0] = pk(h); dst[a.entries[sidx]] = pk(m); dst[2 * a.entries[sidx]] = pk(l);
+  u32x4* dst = dst_p + d;
+  dst[0] = pk(h); dst[ent] = pk(m); dst[2 * ent] = pk(l);
 }
 
 // f16x2 weights: the same fragment order with two pieces, scaled by the layer's weight scale in force (Split16State::sW); the
@@ -765,50 +773,74 @@ struct Pack2Args {
   int nfwd;                        // number of forward-orientation segments = layers (they come first)
   Split16State* st;
 };
+// Every fact of the segment is WAVE-UNIFORM: segment sizes are multiples of 64 entries, so the wave's first entry decides the segment
+// for all of its lanes, and the record (matrix, extents, destination, scale pointer, layer) comes out of the kernel-argument block
+// through scalar loads.  (Indexed per lane, the by-value argument block was read with vector loads from a VGPR address, field by field
+// inside every predicated element: pointer -> extents -> weight, 48 dependent round trips on one thread's path.)  The eight weights of a
+// lane are requested back to back, dead elements re-reading W[0] (Stager::load's idiom, lp_kernels.h), and only then consumed; the
+// path of a thread is record -> weights (+ scale) -> stores.
 __device__ __forceinline__ void pack2_block(const Pack2Args& a, const unsigned block) {
-  const int64_t idx = (int64_t)block * 256 + threadIdx.x;
-  const bool live = idx < a.first[a.nseg];
+  const unsigned wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), ln = threadIdx.x & 63u;
+  const int64_t idx_w = (int64_t)block * 256 + wv * 64u;      // the wave's first entry
+  const bool live = idx_w < a.first[a.nseg];                  // (whole waves: the total is a multiple of 64 as well)
   // (no early return: whole waves take part in the maximum; a wave never straddles two segments' amax slots because segment
   //  sizes are multiples of 64 entries)
   int sidx = 0;
 #pragma unroll
-  for (int i = 1; i < MAXSEG; ++i) sidx += (i < a.nseg && idx >= a.first[i]) ? 1 : 0;
-  const PackSeg& sg = a.seg[sidx];
-  const unsigned d = live ? (unsigned)(idx - a.first[sidx]) : 0u;
+  for (int i = 1; i < MAXSEG; ++i) sidx += (i < a.nseg && idx_w >= a.first[i]) ? 1 : 0;
+  const PackSeg sg = a.seg[sidx];
+  const float* const scale_p = a.scale[sidx];
+  u32x4* dst_p = a.dst[sidx];
+  int64_t ent = a.entries[sidx];
+  int layer = a.layer[sidx];
+  const int64_t first_s = a.first[sidx];
+  const unsigned frag = live ? (unsigned)((idx_w - first_s) >> 6) : 0u;
+  const unsigned d = live ? frag * 64u + ln : 0u;
   const unsigned kiters = (unsigned)(sg.cols + KI - 1) / KI;
-  const unsigned lane = d & 63u, frag = d >> 6;
+  const unsigned lane = d & 63u;
   const unsigned cb = frag / kiters, ki = frag - cb * kiters;
   const int n = (int)(cb * 16u + (lane & 15u)), k = (int)(ki * KI + 8u * (lane >> 4));
-  const float sc = *a.scale[sidx];
+  const int64_t sn = sg.transposed ? 1 : sg.ldw, sk = sg.transposed ? sg.ldw : 1;      // W[kk][n] or W[n][kk]
+  float w[8];
+  bool ok[8];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    ok[u] = live && n < sg.rows && k + u < sg.cols;
+    w[u] = sg.W[ok[u] ? (int64_t)n * sn + (int64_t)(k + u) * sk : 0];
+  }
+  const float sc = *scale_p;
+  asm volatile("" : "+s"(dst_p), "+s"(ent), "+s"(layer));      // the whole record in scalar registers before the weights arrive (read lazily
+                                                               // it was one more scalar round trip between the weights and the stores)
   unsigned hw[4], lw[4];
   float m = 0.f;
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
-    f32x2s v = {0.f, 0.f};
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int kk = k + 2 * u + e;
-      if (live && n < sg.rows && kk < sg.cols) v[e] = sc * (sg.transposed ? sg.W[(int64_t)kk * sg.ldw + n] : sg.W[(int64_t)n * sg.ldw + kk]);
-    }
+    const f32x2s v = {ok[2 * u] ? sc * w[2 * u] : 0.f, ok[2 * u + 1] ? sc * w[2 * u + 1] : 0.f};
     m = fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1])));
     split16_pair(v, hw[u], lw[u]);
   }
   if (live) {
-    u32x4* dst = a.dst[sidx] + d;
+    u32x4* dst = dst_p + d;
     dst[0] = (u32x4){hw[0], hw[1], hw[2], hw[3]};
-    dst[a.entries[sidx]] = (u32x4){lw[0], lw[1], lw[2], lw[3]};
+    dst[ent] = (u32x4){lw[0], lw[1], lw[2], lw[3]};
   }
   // this wave's slot: max |W| (true units) and the layer it belongs to
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-  const unsigned wid = (unsigned)(idx >> 6);
-  if ((threadIdx.x & 63) == 0 && wid < kS16CapPW && a.layer[sidx] >= 0) s16_partW(a.st)[wid] = __float_as_uint((m <= 3.0e38f) ? m / sc : 3.4e38f);
-  if ((threadIdx.x & 63) == 0 && !(m <= kF16Alarm)) s16::s16_raise_poison(a.st);      // the guard: a weight that does not fit its layer's scale (parameters set from outside)
+  const unsigned wid = (unsigned)(idx_w >> 6);
+  if (ln == 0 && wid < kS16CapPW && layer >= 0) s16_partW(a.st)[wid] = __float_as_uint((m <= 3.0e38f) ? m / sc : 3.4e38f);
+  if (ln == 0 && !(m <= kF16Alarm)) s16::s16_raise_poison(a.st);      // the guard: a weight that does not fit its layer's scale (parameters set from outside)
   if (block == 0 && threadIdx.x == 0) s16::s16_refresh_gen(a.st);
-  if (block == 0 && threadIdx.x <= Split16State::NT) {      // wave ranges of the layers (forward-orientation segments come first, one per layer)
-    const int l = threadIdx.x;
-    a.st->wfirst[l] = (unsigned)(a.first[l < a.nfwd ? l : a.nfwd] >> 6);
-    if (l == 0) a.st->nPW = (unsigned)(a.first[a.nfwd] >> 6);
+  if (block == 0 && wv == 0) {      // wave ranges of the layers (forward-orientation segments come first, one per layer)
+    const int64_t first_n = a.first[a.nfwd];
+    unsigned wf = 0u;
+#pragma unroll
+    for (int l = 0; l <= Split16State::NT; ++l) {      // uniform l: scalar reads of the argument block at constant offsets
+      const unsigned f = (unsigned)((l < a.nfwd ? a.first[l] : first_n) >> 6);
+      wf = (int)ln == l ? f : wf;
+    }
+    if (ln <= (unsigned)Split16State::NT) a.st->wfirst[ln] = wf;
+    if (ln == 0) a.st->nPW = (unsigned)(first_n >> 6);
   }
 }
 __global__ __launch_bounds__(256) void mlp_pack2_k(Pack2Args a) { pack2_block(a, blockIdx.x); }
@@ -892,7 +924,7 @@ struct SplitArgs {
     unsigned short* planes; unsigned long long* mask_out;
     int N, pl_units, pl_ones, fast_kind;          // fast_kind: 0 generic epilogue, 1 forward hidden layer, 3 backward link (split_epilogue_fast)
     int boff, K; long long off3, ent3;
-    int pad[2];
+    const float* bias;                            // (the prologue's bias staging reads bias, N and boff of every layer: one line per layer)
   } q[MAXL];
   // (last: the fields above keep their kernel-argument offsets)  The launch's input is the encoder OUTPUT y of a step on the MSE objective (clica_mse_target, include/clica.h): the prologue forms
   // dY = (y - t) * scale for its rows, writes it for the tail and the last layer's weight gradient, feeds it to the first link, and every
@@ -1407,6 +1439,30 @@ __device__ __forceinline__ void tail_wgrad(const SplitArgs::Tail& T, int64_t row
   }
 }
 
+// Bias staging of mlp_split_k's prologue (both arithmetics).  The layer index is UNIFORM: bias pointer, N and the row's offset come out
+// of the layers' quick records in the kernel-argument block through scalar loads (all of them requested before the first is used), thread
+// i < N_l requests bias_l[i] (a layer is at most MAXW <= THREADS wide: one value per thread and layer), and the MAXL requests leave back
+// to back with no wait for memory between them -- a null bias, a column >= N and a layer >= L re-read the zero page and so yield 0 without
+// a select behind the load.  The values are consumed by store_bias_rows, behind every other request of the prologue.
+static_assert(MAXW <= THREADS, "bias staging: one value per thread and layer");
+__device__ __forceinline__ void request_bias_rows(const SplitArgs& a, float (&bv)[MAXL]) {
+  const float* bp[MAXL];
+  int bn[MAXL];
+#pragma unroll
+  for (int l = 0; l < MAXL; ++l) { bp[l] = a.q[l].bias; bn[l] = a.q[l].N; }
+#pragma unroll
+  for (int l = 0; l < MAXL; ++l) {
+    const bool ok = (l < a.g.L) & (bp[l] != nullptr) & ((int)threadIdx.x < bn[l]);
+    bv[l] = *(ok ? bp[l] + threadIdx.x : g_zero_page);
+  }
+}
+// ... into the LDS table: row l at boff[l], zero-padded to a multiple of KI
+__device__ __forceinline__ void store_bias_rows(const SplitArgs& a, float* bias_lds, const float (&bv)[MAXL]) {
+#pragma unroll
+  for (int l = 0; l < MAXL; ++l)
+    if (l < a.g.L && (int)threadIdx.x < ((a.q[l].N + KI - 1) & ~(KI - 1))) bias_lds[a.q[l].boff + threadIdx.x] = bv[l];
+}
+
 template <int AR>
 __global__ __launch_bounds__(THREADS) void mlp_split_k(SplitArgs a) {
   constexpr int NP = Arith<AR>::NP;
@@ -1425,10 +1481,12 @@ __global__ __launch_bounds__(THREADS) void mlp_split_k(SplitArgs a) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned long long*>(p) + (p ? (int64_t)blockIdx.x * WAVES * 64 : 0), 0,
                                              p ? WAVES * 64 * 8 : 0, kRsrcWord3);
   };
-  // Prologue.  Everything it needs from memory is REQUESTED first -- the first layer's weights, the sign bits, every layer's bias,
-  // the input rows, the mixing weights -- and only then consumed: the trace showed 27.9 k cycles (12 % of the forward launch)
-  // between kernel entry and the first layer when each of these was a dependent round trip of its own (seven bias loops, the
-  // input, three mixing layers reading their weights from global memory), all of them cold.
+  // Prologue.  Everything it needs from memory is REQUESTED first -- the first layer's weights, the tail's touches, the sign bits, the
+  // scales, every layer's bias (request_bias_rows), the input rows, the mixing weights -- with no wait between the requests, and only
+  // then consumed (the LDS stores below are the first users).  Every address is formed from scalar registers plus the thread index:
+  // no request waits for another request's data.  (Until the bias loop chose its layer per THREAD it read the layer's record from the
+  // argument block with vector loads: record -> extents -> value, three dependent round trips per unrolled iteration, each vmcnt(0)
+  // also waiting for the cold first-layer weights requested above it.)
   u32x4 wpre[NP][CBW];
   request_first_w3<NP>(a.packed3 + a.off3[0], a.ent3[0], g.layer[0].K, g.layer[0].N, wave, lane, wpre);
   // the tail's wide operand of the last layer (tail_wgrad) comes from HBM, cold: its 48 rows are touched HERE (one load per 128 bytes,
@@ -1459,26 +1517,12 @@ __global__ __launch_bounds__(THREADS) void mlp_split_k(SplitArgs a) {
     if (threadIdx.x < Split16State::NT) amax_lds[threadIdx.x] = 0u;
     if ((int)threadIdx.x < g.L) {
       const int l = threadIdx.x;
-      sc_out = (l == g.L - 1 && a.last_unscaled) ? 1.f : a.s_t[l + 1];
+      sc_out = a.s_t[l + 1];                              // (unconditional: overwriting a requested register costs a vmcnt(0) right here)
       sc_in = a.s_t[l]; sc_w = a.s_w[l];
     }
   }
-  constexpr int BIAS_IT = (BIAS_LDS_MAX + THREADS - 1) / THREADS;
-  float bv[BIAS_IT];
-  const int btotal = a.boff[g.L];
-#pragma unroll
-  for (int u = 0; u < BIAS_IT; ++u) {
-    const int idx = threadIdx.x + u * THREADS;
-    bv[u] = 0.f;
-    if (idx < btotal) {
-      int l = 0;
-#pragma unroll
-      for (int q = 1; q < MAXL; ++q) l += (q < g.L && idx >= a.boff[q]) ? 1 : 0;
-      const Layer& ly = g.layer[l];
-      const int i = idx - a.boff[l];
-      if (ly.bias && i < ly.N) bv[u] = ly.bias[i];
-    }
-  }
+  float bv[MAXL];
+  request_bias_rows(a, bv);
   float s_in0 = 1.f, in_max = 0.f;                     // f16x2: scale of the launch's input tensor, running max of its scaled magnitudes
   if constexpr (AR == 1) s_in0 = a.s_t[0];
   auto store_split = [&](int r, int k, float v) {
@@ -1507,8 +1551,7 @@ __global__ __launch_bounds__(THREADS) void mlp_split_k(SplitArgs a) {
         xv[u] = (idx < ROWS * n && r < nrows) ? g.X[(row0 + r) * g.ldx + k] : 0.f;
         wv[u] = idx < g.mixL * n * n ? g.mixW[idx] : 0.f;
       }
-#pragma unroll
-      for (int u = 0; u < BIAS_IT; ++u) { const int idx = threadIdx.x + u * THREADS; if (idx < btotal) bias_lds[idx] = bv[u]; }
+      store_bias_rows(a, bias_lds, bv);
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         const int idx = threadIdx.x + u * THREADS;
@@ -1535,9 +1578,9 @@ __global__ __launch_bounds__(THREADS) void mlp_split_k(SplitArgs a) {
 #pragma unroll
       for (int u = 0; u < 2; ++u) { const int idx = threadIdx.x + u * THREADS; v[u] = idx < ROWS * n ? xa[idx] : 0.f; }
       ST_STAMP(MAXL - 1, 3);
-      __syncthreads();
-      for (int idx = threadIdx.x; idx < ROWS * K16; idx += THREADS) { const int r = idx / K16; store_split(r, idx - r * K16, 0.f); }
-      __syncthreads();
+      __syncthreads();                                   // the mixing corner is read: the panel may overwrite it
+      // the padding columns k in [K0, K16) of the input panel (the value stores below write every k < K0 of all ROWS rows)
+      for (int idx = threadIdx.x; idx < ROWS * (K16 - n); idx += THREADS) { const int r = idx / (K16 - n); store_split(r, n + idx - r * (K16 - n), 0.f); }
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         const int idx = threadIdx.x + u * THREADS;
@@ -1610,13 +1653,13 @@ __global__ __launch_bounds__(THREADS) void mlp_split_k(SplitArgs a) {
       }
       if (E.t)
         mse::wave_arrive(mse_sq, E.part, (int)blockIdx.x * WAVES + wave, (int)gridDim.x * WAVES, E.arrive, E.loss, E.inv_count, E.tick);
-#pragma unroll
-      for (int u = 0; u < BIAS_IT; ++u) { const int idx = threadIdx.x + u * THREADS; if (idx < btotal) bias_lds[idx] = bv[u]; }
+      store_bias_rows(a, bias_lds, bv);
     }
   }
   if constexpr (AR == 1) {
     if ((int)threadIdx.x < g.L) {
       const int l = threadIdx.x;
+      if (l == g.L - 1 && a.last_unscaled) sc_out = 1.f;
       lscale[l] = sc_out / (sc_in * sc_w); lscale[MAXL + l] = sc_out; lscale[2 * MAXL + l] = 1.f / sc_out;
     }
   }
@@ -2173,7 +2216,7 @@ static int launch_split(fmlp::SplitArgs& a, int arith, clica_stream_t stream, co
     const Layer& ly = a.g.layer[l];
     SplitArgs::LayerQ& q = a.q[l];
     q.planes = ly.planes; q.mask_out = ly.mask_out; q.N = ly.N; q.K = ly.K; q.pl_units = ly.pl_units; q.pl_ones = ly.pl_ones;
-    q.boff = a.boff[l]; q.off3 = a.off3[l]; q.ent3 = a.ent3[l];
+    q.boff = a.boff[l]; q.off3 = a.off3[l]; q.ent3 = a.ent3[l]; q.bias = ly.bias;
     // the combinations the training step runs (see split_epilogue_fast): plane copy only, slope in (0, 1), and either
     // bias + LeakyReLU + sign bits (forward hidden layer) or the sign-bit gate (backward link)
     q.fast_kind = 0;
