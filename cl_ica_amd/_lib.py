@@ -81,6 +81,9 @@ SIGNATURES: Dict[str, list] = {
     "clica_lp_loss_set_matrix_cores": [c_i32],
     "clica_lp_loss_train_spread": [C.POINTER(LpLossDesc), C.c_void_p, c_size, C.POINTER(C.c_float), C.c_void_p],
     "clica_lp_loss_train_guard": [C.POINTER(LpLossDesc), C.c_void_p, c_size, C.POINTER(C.c_float), C.c_void_p],
+    "clica_lp_loss_train_state_bytes": [C.POINTER(c_size)],
+    "clica_lp_loss_train_state_export": [C.POINTER(LpLossDesc), C.c_void_p, c_size, C.c_void_p, c_size, C.c_void_p],
+    "clica_lp_loss_train_state_import": [C.POINTER(LpLossDesc), C.c_void_p, c_size, C.c_void_p, c_size, C.c_void_p],
     "clica_lp_loss_set_spread_limit": [C.c_float],
     "clica_lp_loss_fwd_train": [C.POINTER(LpLossDesc), c_f32p, c_i64, c_f32p, c_i64, c_f32p, c_i64, c_f32p, c_f32p, c_f32p,
                                 c_f32p, c_i64, c_f32p, c_i64, C.c_void_p, c_size, C.c_void_p],
@@ -143,6 +146,9 @@ SIGNATURES: Dict[str, list] = {
     "clica_split16_guard": [C.c_void_p, C.POINTER(c_i32), C.POINTER(c_i32), C.POINTER(c_i32), C.POINTER(c_i32), C.c_void_p],
     "clica_split16_set_dp_poison": [C.c_void_p, C.c_void_p, C.c_void_p],
     "clica_split16_poison_export": [C.c_void_p, C.c_void_p, C.c_void_p],
+    "clica_split16_export_bytes": [C.POINTER(c_size)],
+    "clica_split16_export": [C.c_void_p, c_i32, C.c_void_p, c_size, C.c_void_p],
+    "clica_split16_import": [C.c_void_p, C.c_void_p, c_size, c_i32, C.c_void_p],
     "clica_mlp_planes16_bytes": [c_i64, c_i32, c_i32, C.POINTER(c_size)],
     "clica_mlp_pack_split16_bytes": [c_i32, C.POINTER(c_i32), C.POINTER(c_i32), c_i32, C.POINTER(c_size)],
     "clica_mlp_pack_split16_both": [c_i32, C.POINTER(C.c_void_p), C.POINTER(c_i64), C.POINTER(c_i32), C.POINTER(c_i32), C.c_void_p, C.c_void_p,

@@ -2473,6 +2473,82 @@ extern "C" int clica_split16_clear_flags(void* state, clica_stream_t stream) {
     return launch_status("clica_split16_clear_flags");
   return CLICA_OK;
 }
+// ---- portable form of the state at a step boundary (checkpoints) ---------------------------------------------------------------------
+// What the next step reads of its predecessors: the scales in force (sA / sD / sW / sWC), the scales the last step ran with (pA / pD),
+// flags, the generation (`updates`), the guard's words (poison, gen_copy) and the withheld-step count.  NOT exported: dp_poison (an
+// address of the exporting process), the capacities, and what is empty between steps or rewritten before it is read -- the live-slot
+// counts and the slot arrays (zero behind every update), the pack waves (nPW, wfirst, partW: written by the next step's weight pack).
+// Blob, 64 words: [0] layout version, [1] n_layers, [2] flags, [3] updates, [4] poison, [5] gen_copy, [6] skipped, [7] 0, then
+// sA, sD, sW, sWC, pA, pD (NT floats each).
+namespace clica { namespace fmlp {
+constexpr unsigned kS16BlobVersion = 1u;
+constexpr int kS16BlobWords = 64;
+static_assert(8 + 6 * Split16State::NT <= kS16BlobWords, "the blob holds six scale arrays behind its eight header words");
+__global__ __launch_bounds__(64) void split16_export_k(const Split16State* __restrict__ st, unsigned* __restrict__ blob, unsigned L) {
+  constexpr int NT = Split16State::NT;
+  const int t = threadIdx.x;
+  unsigned v = 0u;
+  if (t == 0) v = kS16BlobVersion;
+  else if (t == 1) v = L;
+  else if (t == 2) v = st->flags;
+  else if (t == 3) v = st->updates;
+  else if (t == 4) v = st->poison;
+  else if (t == 5) v = st->gen_copy;
+  else if (t == 6) v = st->skipped;
+  else if (t >= 8 && t < 8 + 6 * NT) {
+    const int a = (t - 8) / NT, k = (t - 8) - a * NT;
+    const float* src = a == 0 ? st->sA : (a == 1 ? st->sD : (a == 2 ? st->sW : (a == 3 ? st->sWC : (a == 4 ? st->pA : st->pD))));
+    v = __float_as_uint(src[k]);
+  }
+  blob[t] = v;
+}
+// workgroup 0 installs the header words; every workgroup zeroes its share of the slot arrays (the between-steps condition)
+__global__ __launch_bounds__(256) void split16_import_k(Split16State* __restrict__ st, const unsigned* __restrict__ blob) {
+  constexpr int NT = Split16State::NT;
+  const unsigned nslots = 3u * NT * kS16CapWG;
+  unsigned* slots = s16_partA(st);
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < nslots; i += gridDim.x * 256u) slots[i] = 0u;
+  if (blockIdx.x != 0) return;
+  const int t = threadIdx.x;
+  if (t < NT) st->cntA[t] = st->cntD[t] = st->cntW[t] = 0u;
+  if (t == 0) { st->nPW = 0u; st->flags = blob[2]; st->updates = blob[3]; st->poison = blob[4]; st->gen_copy = blob[5]; st->skipped = blob[6]; }
+  if (t >= 8 && t < 8 + 6 * NT) {
+    const int a = (t - 8) / NT, k = (t - 8) - a * NT;
+    float* dst = a == 0 ? st->sA : (a == 1 ? st->sD : (a == 2 ? st->sW : (a == 3 ? st->sWC : (a == 4 ? st->pA : st->pD))));
+    dst[k] = __uint_as_float(blob[t]);
+  }
+}
+} }
+extern "C" int clica_split16_export_bytes(size_t* bytes) {
+  CLICA_CHECK_ARG(bytes != nullptr, "clica_split16_export_bytes: bytes is NULL");
+  *bytes = (size_t)fmlp::kS16BlobWords * sizeof(unsigned);
+  return CLICA_OK;
+}
+extern "C" int clica_split16_export(const void* state, int32_t n_layers, void* blob, size_t blob_bytes, clica_stream_t stream) {
+  CLICA_CHECK_ARG(state != nullptr && blob != nullptr, "clica_split16_export: NULL argument");
+  CLICA_CHECK_ARG(n_layers >= 1 && n_layers <= fmlp::MAXL, "clica_split16_export: n_layers = %d (1..%d)", n_layers, fmlp::MAXL);
+  CLICA_CHECK_ARG(blob_bytes >= (size_t)fmlp::kS16BlobWords * sizeof(unsigned), "clica_split16_export: blob of %zu bytes < %zu", blob_bytes,
+                  (size_t)fmlp::kS16BlobWords * sizeof(unsigned));
+  hipLaunchKernelGGL(fmlp::split16_export_k, dim3(1), dim3(fmlp::kS16BlobWords), 0, as_stream(stream),
+                     reinterpret_cast<const fmlp::Split16State*>(state), reinterpret_cast<unsigned*>(blob), (unsigned)n_layers);
+  return launch_status("clica_split16_export");
+}
+extern "C" int clica_split16_import(void* state, const void* blob, size_t blob_bytes, int32_t n_layers, clica_stream_t stream) {
+  CLICA_CHECK_ARG(state != nullptr && blob != nullptr, "clica_split16_import: NULL argument");
+  CLICA_CHECK_ARG(n_layers >= 1 && n_layers <= fmlp::MAXL, "clica_split16_import: n_layers = %d (1..%d)", n_layers, fmlp::MAXL);
+  CLICA_CHECK_ARG(blob_bytes >= (size_t)fmlp::kS16BlobWords * sizeof(unsigned), "clica_split16_import: blob of %zu bytes < %zu", blob_bytes,
+                  (size_t)fmlp::kS16BlobWords * sizeof(unsigned));
+  hipStream_t st = as_stream(stream);
+  unsigned head[2];
+  if (hipMemcpyAsync(head, blob, sizeof(head), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return launch_status("clica_split16_import");
+  CLICA_CHECK_ARG(head[0] == fmlp::kS16BlobVersion, "clica_split16_import: blob layout version %u (this library reads version %u)", head[0],
+                  fmlp::kS16BlobVersion);
+  CLICA_CHECK_ARG(head[1] == (unsigned)n_layers, "clica_split16_import: the blob was exported from an encoder of %u layers, not %d", head[1], n_layers);
+  hipLaunchKernelGGL(fmlp::split16_import_k, dim3(108), dim3(256), 0, st, reinterpret_cast<fmlp::Split16State*>(state),
+                     reinterpret_cast<const unsigned*>(blob));
+  return launch_status("clica_split16_import");
+}
 extern "C" int clica_mlp_pack_split16_bytes(int32_t n_layers, const int32_t* N, const int32_t* K, int32_t transpose, size_t* bytes) {
   using namespace fmlp;
   CLICA_CHECK_ARG(N && K && bytes && n_layers >= 1 && n_layers <= MAXL, "clica_mlp_pack_split16_bytes: bad argument");

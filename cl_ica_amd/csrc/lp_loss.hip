@@ -543,6 +543,69 @@ extern "C" int clica_lp_loss_train_guard(const clica_lp_loss_desc* d, const void
   return CLICA_OK;
 }
 
+// ---- portable form of what a training loop's workspace carries from one call to the next (checkpoints) -----------------------------
+// The state is the 64 guard / grid words in front of the matrix-core planes (lp_mfma.h): largest and last M, the violation word, the call
+// id, the fallback counter, max |x'| of the current and the next grid, the three origins.  Planes, row statistics and partials are
+// rewritten by every call, the arrival counters are zero between calls: not state.  Blob: [0] layout version (0: no state), [1] number
+// of words, [2], [3] zero, then the words.
+namespace clica { namespace lp {
+constexpr unsigned kTrainStateVersion = 1u;
+constexpr int kTrainStateWords = 64;
+constexpr size_t kTrainStateBytes = (4 + kTrainStateWords) * sizeof(unsigned);
+__global__ __launch_bounds__(64) void train_state_export_k(const unsigned* __restrict__ words, unsigned* __restrict__ blob) {
+  const int t = threadIdx.x;
+  if (t < 4) blob[t] = t == 0 ? kTrainStateVersion : (t == 1 ? (unsigned)kTrainStateWords : 0u);
+  if (t < kTrainStateWords) blob[4 + t] = words[t];
+}
+__global__ __launch_bounds__(64) void train_state_import_k(unsigned* __restrict__ words, const unsigned* __restrict__ blob) {
+  const int t = threadIdx.x;
+  if (t < kTrainStateWords) words[t] = blob[4 + t];
+}
+} }
+extern "C" int clica_lp_loss_train_state_bytes(size_t* bytes) {
+  CLICA_CHECK_ARG(bytes != nullptr, "clica_lp_loss_train_state_bytes: bytes is NULL");
+  *bytes = kTrainStateBytes;
+  return CLICA_OK;
+}
+extern "C" int clica_lp_loss_train_state_export(const clica_lp_loss_desc* d, const void* workspace, size_t workspace_bytes, void* blob,
+                                                size_t blob_bytes, clica_stream_t stream) {
+  int rc = validate(d, "clica_lp_loss_train_state_export");
+  if (rc) return rc;
+  CLICA_CHECK_ARG(workspace && blob, "clica_lp_loss_train_state_export: NULL pointer");
+  CLICA_CHECK_ARG(blob_bytes >= kTrainStateBytes, "clica_lp_loss_train_state_export: blob of %zu bytes < %zu", blob_bytes, kTrainStateBytes);
+  hipStream_t st = as_stream(stream);
+  if (!train_mfma(d)) {      // VALU sweeps only: nothing is carried between calls
+    if (hipMemsetAsync(blob, 0, kTrainStateBytes, st) != hipSuccess) return launch_status("clica_lp_loss_train_state_export");
+    return CLICA_OK;
+  }
+  const int64_t rows = d->B, cols = d->B3;
+  TrainWs w = carve_train(const_cast<void*>(workspace), make_plan(rows, cols, d->n, false), make_plan(rows, cols, d->n, true), rows, cols, true);
+  if (w.bytes > workspace_bytes) { set_error("clica_lp_loss_train_state_export: workspace %zu < %zu", workspace_bytes, w.bytes); return CLICA_E_WORKSPACE; }
+  hipLaunchKernelGGL(train_state_export_k, dim3(1), dim3(64), 0, st, reinterpret_cast<const unsigned*>(w.w2.spread), reinterpret_cast<unsigned*>(blob));
+  return launch_status("clica_lp_loss_train_state_export");
+}
+extern "C" int clica_lp_loss_train_state_import(const clica_lp_loss_desc* d, void* workspace, size_t workspace_bytes, const void* blob,
+                                                size_t blob_bytes, clica_stream_t stream) {
+  int rc = validate(d, "clica_lp_loss_train_state_import");
+  if (rc) return rc;
+  CLICA_CHECK_ARG(workspace && blob, "clica_lp_loss_train_state_import: NULL pointer");
+  CLICA_CHECK_ARG(blob_bytes >= kTrainStateBytes, "clica_lp_loss_train_state_import: blob of %zu bytes < %zu", blob_bytes, kTrainStateBytes);
+  if (!train_mfma_shape(d)) return CLICA_OK;      // this workspace has no such words
+  const int64_t rows = d->B, cols = d->B3;
+  TrainWs w = carve_train(workspace, make_plan(rows, cols, d->n, false), make_plan(rows, cols, d->n, true), rows, cols, true);
+  if (w.bytes > workspace_bytes) { set_error("clica_lp_loss_train_state_import: workspace %zu < %zu", workspace_bytes, w.bytes); return CLICA_E_WORKSPACE; }
+  hipStream_t st = as_stream(stream);
+  unsigned head[4];
+  if (hipMemcpyAsync(head, blob, sizeof(head), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return launch_status("clica_lp_loss_train_state_import");
+  if (head[0] == 0u) return CLICA_OK;             // saved from the VALU sweeps: the words stay as they are
+  CLICA_CHECK_ARG(head[0] == kTrainStateVersion && head[1] == (unsigned)kTrainStateWords,
+                  "clica_lp_loss_train_state_import: blob layout version %u with %u words (this library reads version %u, %d words)",
+                  head[0], head[1], kTrainStateVersion, kTrainStateWords);
+  hipLaunchKernelGGL(train_state_import_k, dim3(1), dim3(64), 0, st, reinterpret_cast<unsigned*>(w.w2.spread), reinterpret_cast<const unsigned*>(blob));
+  return launch_status("clica_lp_loss_train_state_import");
+}
+
 extern "C" int clica_lp_loss_fwd_train(const clica_lp_loss_desc* d,
                                        const float* z1, int64_t ld1, const float* z2, int64_t ld2, const float* pool, int64_t ldp,
                                        float* loss_i, float* pos_i, float* lse_i,

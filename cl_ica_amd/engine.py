@@ -17,6 +17,7 @@ flat gradient arena; semantics = the single-process loss on the concatenated bat
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import os
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence
@@ -973,10 +974,160 @@ class ContrastiveTrainer:
         """Which encoder arithmetic runs and, for f16x2, the state of its scales (host read + sync: log points, tests).  A non-zero
         `flags` means a tensor outgrew its scale by more than 64 x within one step: the step that raised it is not to be trusted."""
         if self.s16 is not None:
-            return dict(arith="f16x2" if self.split_f16 else "f16x2 (per-layer wide path; narrow layers native fp32 MFMA)", **self.s16.read())
+            return dict(arith=self._arith_name(), **self.s16.read())
+        return dict(arith=self._arith_name())
+
+    def _arith_name(self) -> str:
+        """The `arith` string of arith_state() (no device read)."""
+        if self.s16 is not None:
+            return "f16x2" if self.split_f16 else "f16x2 (per-layer wide path; narrow layers native fp32 MFMA)"
         if not (self.split_bf16 or getattr(self, "split_wgrad_wide", False)):
-            return dict(arith="native_fp32")
-        return dict(arith="bf16x3")
+            return "native_fp32"
+        return "bf16x3"
+
+    # -------------------------------------------------------------------------------- checkpoints
+    STATE_FORMAT, STATE_VERSION = "cl_ica_amd.trainer", 1
+    _kind = "contrastive"
+
+    def _head_name(self) -> str:
+        if self.head is None:
+            return "none"
+        return f"{type(self.head).__name__}({'learnable' if self.head_learnable else 'fixed'})"
+
+    def _config(self) -> dict:
+        """Everything that decides the trajectory of a run besides its state (state_dict()["config"]; load_state_dict(strict=True)
+        compares it field by field)."""
+        samp = dataclasses.asdict(self.sampler)
+        samp["box"] = [float(v) for v in samp["box"]]
+        return dict(sampler=samp, batch_size=self.B, p=self.p, tau=self.tau, alpha=self.alpha, g_weights=self.gW.detach().cpu().clone(),
+                    g_slope=self.g_slope, g_act_kind=self.g_act_kind, world=self.world, dry_ranks=self.dry_ranks,
+                    layer_shapes=[[int(lin.out_features), int(lin.in_features)] for lin in self.linears], head=self._head_name())
+
+    def _not_in_capture(self, what: str):
+        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{what} inside a graph capture: it reads / writes the trainer's state from the host")
+
+    def state_dict(self) -> dict:
+        """Everything the next step depends on, as a plain dict of CPU tensors, numbers, strings, lists and dicts (survives torch.save /
+        torch.load(weights_only=True)): the encoder's state dict (`f`: the reference's keys, what {sup,unsup}_f.pth holds), the Adam
+        moments in torch.optim.Adam's layout (`optimizer`: interchangeable with cl_ica_amd.optim.Adam and torch.optim.Adam over
+        f.parameters()), the device step / RNG counter (`step`), the configuration the trajectory depends on (`config`) and what the
+        arithmetic carries from step to step (`arith`: the f16x2 scales and guard words, the matrix-core loss sweeps' grid and guard
+        words -- opaque blobs written by the library, None where the trainer has no such state).  Between steps only: one
+        synchronisation, never inside a capture."""
+        self._not_in_capture("state_dict()")
+        cuda = self.device.type == "cuda"
+        s16_blob = self.s16.export_state() if self.s16 is not None else None
+        loss_blob = ops.lp_loss_train_state_export(self.desc, self.loss_ws) if (cuda and self.loss_train and not self.dot) else None
+        f_sd = self.f.state_dict()
+        dev = [self.exp_avg, self.exp_avg_sq, self.step_dev] + list(f_sd.values()) + [b for b in (s16_blob, loss_blob) if b is not None]
+        if cuda:        # every read queued behind the step's launches, one wait for all of them
+            host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t.detach(), non_blocking=True) for t in dev]
+            torch.cuda.current_stream(self.device).synchronize()
+            host = [t.clone() for t in host]
+        else:
+            host = [t.detach().clone() for t in dev]
+        exp_avg, exp_avg_sq, step = host[0], host[1], int(host[2].item())
+        f_host = dict(zip(f_sd.keys(), host[3:3 + len(f_sd)]))
+        blobs = host[3 + len(f_sd):]
+        state, params, off = {}, list(self.f.parameters()), 0
+        for i, prm in enumerate(params):
+            if step > 0:      # (cl_ica_amd.optim.Adam and torch.optim.Adam: no state before the first step)
+                sl = slice(off, off + prm.numel())
+                state[i] = dict(step=torch.tensor(float(step)), exp_avg=exp_avg[sl].view(prm.shape).clone(),
+                                exp_avg_sq=exp_avg_sq[sl].view(prm.shape).clone())
+            off += (prm.numel() + 3) // 4 * 4
+        group = dict(lr=self.lr, betas=(float(self.betas[0]), float(self.betas[1])), eps=self.eps, weight_decay=0, amsgrad=False,
+                     params=list(range(len(params))))
+        arith = dict(arith=self._arith_name(), clica_version=int(_lib.load().clica_version()), s16_calibrated=bool(self._s16_calibrated),
+                     split16=blobs.pop(0) if s16_blob is not None else None, loss=blobs.pop(0) if loss_blob is not None else None)
+        return dict(format=self.STATE_FORMAT, version=self.STATE_VERSION, kind=self._kind, f=f_host,
+                    optimizer=dict(state=state, param_groups=[group]), step=step, config=self._config(), arith=arith)
+
+    def _check_config(self, sd: dict, strict: bool):
+        """ValueError naming the first field of a checkpoint that does not fit this trainer (shapes and kind always; with `strict`
+        everything that changes the trajectory)."""
+        def differ(field, saved, mine):
+            raise ValueError(f"load_state_dict: `{field}` of the checkpoint ({saved!r}) differs from this trainer's ({mine!r})")
+        if sd.get("format") != self.STATE_FORMAT or int(sd.get("version", -1)) != self.STATE_VERSION:
+            raise ValueError(f"load_state_dict: not a {self.STATE_FORMAT} checkpoint of version {self.STATE_VERSION} "
+                             f"(format {sd.get('format')!r}, version {sd.get('version')!r})")
+        if sd["kind"] != self._kind:
+            differ("kind", sd["kind"], self._kind)
+        saved, mine = sd["config"], self._config()
+        if [list(s) for s in saved["layer_shapes"]] != mine["layer_shapes"]:
+            differ("layer_shapes", saved["layer_shapes"], mine["layer_shapes"])
+        want = {k: tuple(v.shape) for k, v in self.f.state_dict().items()}
+        got = {k: tuple(v.shape) for k, v in sd["f"].items()}
+        if want != got:
+            differ("f", got, want)
+        if not strict:
+            return
+        for key in ("head", "batch_size", "p", "tau", "alpha", "g_slope", "g_act_kind", "world", "dry_ranks"):
+            if saved[key] != mine[key]:
+                differ(key, saved[key], mine[key])
+        for key, val in mine["sampler"].items():
+            sv = saved["sampler"].get(key)
+            if (list(sv) if isinstance(sv, (list, tuple)) else sv) != val:
+                differ(f"sampler.{key}", sv, val)
+        if tuple(saved["g_weights"].shape) != tuple(mine["g_weights"].shape) or not torch.equal(saved["g_weights"], mine["g_weights"]):
+            differ("g_weights", tuple(saved["g_weights"].shape), tuple(mine["g_weights"].shape))
+        group = sd["optimizer"]["param_groups"][0]
+        for key, val in (("lr", self.lr), ("eps", self.eps)):      # (kernel arguments of a captured step: they cannot follow the file)
+            if float(group[key]) != val:
+                differ(f"optimizer.{key}", group[key], val)
+        if tuple(float(b) for b in group["betas"]) != (float(self.betas[0]), float(self.betas[1])):
+            differ("optimizer.betas", group["betas"], self.betas)
+
+    def load_state_dict(self, sd: dict, strict: bool = True) -> str:
+        """Continue the run a `state_dict()` was taken from.  Written IN PLACE (copy_ into the arenas and the step counter: every
+        data_ptr() stays, a captured graph stays valid and is not captured again), before or after capture(), on a fresh trainer or one
+        that has stepped.  `strict`: a difference in anything that changes the trajectory -- kind, layer shapes, head, batch size, p / tau /
+        alpha, any SamplerSpec field (seed included), the mixing weights, world, dry_ranks, the optimizer's constants -- raises ValueError
+        naming the field; otherwise only kind and shapes bind.  Returns the domain that applied: "exact" -- the arithmetic and the library
+        version are the saved ones, the blobs of `arith` are installed and the continuation is bit-identical to the uninterrupted run --
+        or "portable": parameters, moments and step are restored exactly, the blobs are ignored and the f16x2 scales are calibrated anew
+        (the counter is put back, so the batch sequence is still the saved run's); agreement within the arithmetic's tolerance."""
+        self._not_in_capture("load_state_dict()")
+        self._check_config(sd, strict)
+        cuda = self.device.type == "cuda"
+        with torch.no_grad():
+            for key, dst in self.f.state_dict().items():          # (views of the parameter arena, and the head's buffers)
+                dst.copy_(sd["f"][key])
+            params, off = list(self.f.parameters()), 0
+            ostate = sd["optimizer"]["state"]
+            for i, prm in enumerate(params):
+                st = ostate.get(i, ostate.get(str(i)))
+                sl = slice(off, off + prm.numel())
+                if st is None:
+                    self.exp_avg[sl].zero_(); self.exp_avg_sq[sl].zero_()
+                else:
+                    self.exp_avg[sl].view(prm.shape).copy_(st["exp_avg"])
+                    self.exp_avg_sq[sl].view(prm.shape).copy_(st["exp_avg_sq"])
+                off += (prm.numel() + 3) // 4 * 4
+            self.step_dev.fill_(int(sd["step"]))
+        arith = sd["arith"]
+        exact = (arith["arith"] == self._arith_name() and int(arith["clica_version"]) == int(_lib.load().clica_version())
+                 and (arith["split16"] is not None) == (self.s16 is not None))
+        if exact:
+            if self.s16 is not None:
+                self.s16.import_state(arith["split16"])
+                self._s16_calibrated = bool(arith["s16_calibrated"])
+                self._guard_skipped_seen = self.s16.guard()["skipped"]
+            if arith["loss"] is not None and cuda and self.loss_train and not self.dot:
+                ops.lp_loss_train_state_import(self.desc, self.loss_ws, arith["loss"])
+        else:
+            self._s16_calibrated = False
+        # the load is not an "external write": what the kernels derive from the parameters is marked stale, nothing is re-measured
+        self._versions_seen = self._param_versions()
+        self._packed_current = False
+        self._x_pending = False
+        self._ticked = self._adam_done = False
+        self._dy_parts = self._mse_fold = None
+        ops.PARAM_EPOCH += 1
+        if not exact and self.s16 is not None and self.graph is not None:
+            self.calibrate_scales(True)        # a replayed graph cannot calibrate on its own (as _check_external_writes does)
+        return "exact" if exact else "portable"
 
     def step(self):
         """One unsupervised step with on-device sampling.  Returns the device tensor
@@ -1120,6 +1271,7 @@ class SupervisedTrainer(ContrastiveTrainer):
 
     # test hook (class attribute, tests/test_gpu_supervised.py): the chain's prologue forms dY (False: the stand-alone launch)
     fold_mse = True
+    _kind = "supervised"
 
     def __init__(self, f: nn.Sequential, g_weights: torch.Tensor, sampler: SamplerSpec, batch_size: int,
                  lr: float = 1e-4, g_slope: float = 0.2, betas=(0.9, 0.999), eps: float = 1e-8, device=None,

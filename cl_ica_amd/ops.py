@@ -211,6 +211,24 @@ class Split16:
     def poison_export(self, slot: torch.Tensor):
         check(load().clica_split16_poison_export(self.buf.data_ptr(), slot.data_ptr(), stream_ptr()), "clica_split16_poison_export")
 
+    def export_state(self) -> torch.Tensor:
+        """The portable part of the state at a step boundary as an opaque device blob (include/clica.h, "CHECKPOINTS": scales, flags,
+        generation, the guard's words -- no addresses, no capacities).  One tiny launch, no sync; `import_state` of another `Split16`
+        of the same number of layers, in this process or another, takes it."""
+        nb = C.c_size_t()
+        check(load().clica_split16_export_bytes(C.byref(nb)), "clica_split16_export_bytes")
+        blob = torch.zeros(nb.value, dtype=torch.uint8, device=self.buf.device)
+        check(load().clica_split16_export(self.buf.data_ptr(), self.n_layers, blob.data_ptr(), blob.numel(), stream_ptr()), "clica_split16_export")
+        return blob
+
+    def import_state(self, blob: torch.Tensor):
+        """Install a blob of `export_state` (a uint8 tensor, any device): the data-parallel verdict slot and the capacities stay this
+        process's, the slot counts go to their between-steps condition.  Synchronises; not inside a graph capture."""
+        if blob.dtype != torch.uint8 or blob.dim() != 1:
+            raise ClicaError(f"Split16.import_state: the blob is a 1-D uint8 tensor (got {blob.dtype}, {blob.dim()} dimensions)")
+        blob = blob.to(self.buf.device).contiguous()
+        check(load().clica_split16_import(self.buf.data_ptr(), blob.data_ptr(), blob.numel(), self.n_layers, stream_ptr()), "clica_split16_import")
+
     def read(self) -> dict:
         fl, up = C.c_int32(), C.c_int32()
         a, d, w, pa, pd = (C.c_float * 9)(), (C.c_float * 9)(), (C.c_float * 9)(), (C.c_float * 9)(), (C.c_float * 9)()
@@ -696,6 +714,32 @@ def stamp_intervals_us(slot: torch.Tensor):
     v = slot.cpu()
     n = min(int(v[0]), (v.numel() - 1) // 2)
     return [(int(v[2 + 2 * i]) - int(v[1 + 2 * i])) / 100.0 for i in range(n)]
+
+
+# ------------------------------------------------------------------------------- loss workspace state (checkpoints)
+def lp_loss_train_state_export(desc, ws: torch.Tensor) -> torch.Tensor:
+    """What the training pair's workspace `ws` carries from call to call (include/clica.h, "CHECKPOINTS": the guard / grid words of the
+    p = 2 matrix-core sweeps) as an opaque device blob; all zero where the calls of `desc` run the VALU sweeps only or `desc` is the dot
+    pair's (nothing carried).  One tiny launch, no sync."""
+    nb = C.c_size_t()
+    check(load().clica_lp_loss_train_state_bytes(C.byref(nb)), "clica_lp_loss_train_state_bytes")
+    blob = torch.zeros(nb.value, dtype=torch.uint8, device=ws.device)
+    if isinstance(desc, _lib.LpLossDesc):
+        check(load().clica_lp_loss_train_state_export(C.byref(desc), ws.data_ptr(), ws.numel(), blob.data_ptr(), blob.numel(), stream_ptr()),
+              "clica_lp_loss_train_state_export")
+    return blob
+
+
+def lp_loss_train_state_import(desc, ws: torch.Tensor, blob: torch.Tensor):
+    """Install a blob of `lp_loss_train_state_export` into the workspace `ws` of the same loss description (a no-op for an all-zero
+    blob, the VALU-only shapes and the dot pair).  Synchronises; not inside a graph capture."""
+    if blob.dtype != torch.uint8 or blob.dim() != 1:
+        raise ClicaError(f"lp_loss_train_state_import: the blob is a 1-D uint8 tensor (got {blob.dtype}, {blob.dim()} dimensions)")
+    if not isinstance(desc, _lib.LpLossDesc):
+        return
+    blob = blob.to(ws.device).contiguous()
+    check(load().clica_lp_loss_train_state_import(C.byref(desc), ws.data_ptr(), ws.numel(), blob.data_ptr(), blob.numel(), stream_ptr()),
+          "clica_lp_loss_train_state_import")
 
 
 # ------------------------------------------------------------------------------- MSE objective

@@ -1,6 +1,8 @@
 """Training driver for the MLP-mixing experiment: the counterpart of /root/reference/main_mlp.py on
 the HIP hot path.  Same command-line flags (main_mlp.py:21-127), same phases (supervised then
-unsupervised), same log lines and checkpoints (g.pth, sup_f.pth, unsup_f.pth).
+unsupervised), same log lines and checkpoints (g.pth, sup_f.pth, unsup_f.pth).  On top of the reference's flags: ``--checkpoint-every N`` writes the
+whole training state of the running phase ({sup,unsup}_trainer.pth: encoder, Adam moments, step / RNG counter, what the arithmetic
+carries between steps, and the driver's own counters) and ``--resume-from FILE`` continues such a run bit for bit.
 
     python -m cl_ica_amd.train_mlp --n 10 --space-type box --p 2 --batch-size 6144 --n-steps 1000
     python -m torch.distributed.run --nproc-per-node 8 -m cl_ica_amd.train_mlp ...      # data parallel
@@ -61,8 +63,48 @@ def parse_args(argv=None):
     for flag, hlp in _SWITCHES:
         ap.add_argument(flag, action="store_true", help=hlp)
     ap.add_argument("--space-type", type=str, default="box", choices=("box", "sphere", "unbounded"))
+    ap.add_argument("--checkpoint-every", type=int, default=0,
+                    help="With --save-dir: write {sup,unsup}_trainer.pth (the full training state) every N steps and at the end of a phase; 0 = off.")
+    ap.add_argument("--resume-from", type=str, default="", help="Continue the run a {sup,unsup}_trainer.pth file was written by.")
     args = ap.parse_args(argv)
+    if args.checkpoint_every < 0:
+        ap.error("--checkpoint-every must be >= 0")
+    if args.resume_from:
+        try:
+            check_resume(args, load_checkpoint(args.resume_from)["driver"])
+        except (OSError, KeyError, ValueError) as e:
+            ap.error(f"--resume-from {args.resume_from}: {e}")
     return args
+
+
+# flags that decide the trajectory of a run: a resumed run must be started with the values its checkpoint was written under
+_TRAJECTORY = ("sphere_r", "box_min", "box_max", "act_fct", "c_param", "m_param", "tau", "n_mixing_layer", "n", "m_p", "c_p", "lr", "p",
+               "batch_size", "space_type", "sphere_norm", "box_norm")
+_PHASE = {True: "sup", False: "unsup"}
+
+
+def load_checkpoint(path):
+    """A {sup,unsup}_trainer.pth file: the trainer's state_dict() plus the `driver` section (plain data: weights_only loading)."""
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(ck, dict) or "driver" not in ck:
+        raise ValueError("not a train_mlp checkpoint (no `driver` section)")
+    return ck
+
+
+def check_resume(args, drv) -> None:
+    """ValueError when the command line contradicts the checkpoint it asks to continue (its --seed, or any trajectory flag)."""
+    if args.seed is not None and int(args.seed) != int(drv["seed"]):
+        raise ValueError(f"--seed {args.seed} contradicts the checkpoint's seed {drv['seed']}")
+    for key in _TRAJECTORY:
+        if getattr(args, key) != drv["args"][key]:
+            raise ValueError(f"--{key.replace('_', '-')} {getattr(args, key)!r} contradicts the checkpoint's {drv['args'][key]!r}")
+
+
+def write_checkpoint(path, payload) -> None:
+    """Atomically: a reader (or a job killed half way) never sees a partial file."""
+    tmp = path + ".tmp"
+    torch.save(payload, tmp)
+    os.replace(tmp, path)
 
 
 _KIND = {0: None, 1: "laplace", 2: "normal"}
@@ -146,7 +188,11 @@ def _main(argv=None):
     log("Arguments:")
     for k, v in vars(args).items():
         log(f"\t{k}: {v}")
-    seed = args.seed if args.seed is not None else int.from_bytes(os.urandom(4), "little")
+    resume = load_checkpoint(args.resume_from) if args.resume_from else None
+    if resume is not None:
+        seed = int(resume["driver"]["seed"])
+    else:
+        seed = args.seed if args.seed is not None else int.from_bytes(os.urandom(4), "little")
     if world > 1:      # without --seed every process would draw its own: rank 0's seed is THE seed (identical g and f everywhere)
         box = [seed]
         torch.distributed.broadcast_object_list(box, src=0)
@@ -172,7 +218,22 @@ def _main(argv=None):
     f = None
     contrastive_engine = False
     supervised_engine = None
+    if resume is not None:
+        if resume["driver"]["phase"] not in [_PHASE[s] for s in phases]:
+            raise SystemExit(f"--resume-from: the checkpoint is of the {resume['driver']['phase']} phase, which this command line does not run")
+        if resume["driver"]["phase_done"] and resume["driver"]["phase"] == _PHASE[phases[-1]]:
+            raise SystemExit("--resume-from: the checkpoint is of a finished run: nothing left to train")
     for supervised in phases:
+        drv = resume["driver"] if resume is not None else None
+        if drv is not None and (_PHASE[supervised] != drv["phase"] or drv["phase_done"]):
+            # a phase the checkpointed run has finished: its record carries over, the run goes on behind it
+            log(f"supervised test: {supervised} (finished in {args.resume_from}: skipped)")
+            if _PHASE[supervised] == drv["phase"]:
+                total_loss_values, lin_scores, perm_scores = list(drv["losses"]), list(drv["lin_scores"]), list(drv["perm_scores"])
+                spaces._state.update(drv["spaces_state"])
+                torch.set_rng_state(drv["torch_rng_state"])
+                resume = None
+            continue
         log(f"supervised test: {supervised}")
         if args.box_norm:
             out_norm = "learnable_box"
@@ -215,6 +276,44 @@ def _main(argv=None):
 
         last_step = args.n_steps if supervised else args.n_steps * args.more_unsupervised
         global_step = len(total_loss_values) + 1
+        if drv is not None:
+            # continue this phase where the checkpoint left it: in place, behind capture() (the graph stays valid); strict -- the file
+            # must be of this very configuration -- and in the exact domain the steps that follow are those of the uninterrupted run
+            if fused:
+                domain = trainer.load_state_dict(resume, strict=True)
+            else:
+                f.load_state_dict(resume["f"]); optimizer.load_state_dict(resume["optimizer"]); domain = "portable"
+            total_loss_values, lin_scores, perm_scores = list(drv["losses"]), list(drv["lin_scores"]), list(drv["perm_scores"])
+            global_step = int(drv["global_step"])
+            lin, perm = (lin_scores[-1], perm_scores[-1]) if lin_scores else (lin, perm)
+            spaces._state.update(drv["spaces_state"])
+            torch.set_rng_state(drv["torch_rng_state"])
+            log(f"resumed from {args.resume_from}: step {global_step} of the {drv['phase']} phase ({domain} domain)")
+            resume = None
+
+        def checkpoint(done: bool):
+            """{sup,unsup}_trainer.pth: the trainer's state (the autograd fallback: f and the flat Adam in the same slots) + the driver's."""
+            nonlocal pending
+            if pending:
+                total_loss_values.extend(float(v) for v in torch.stack(pending).cpu())
+                pending = []
+            if fused:
+                payload = trainer.state_dict()
+            else:
+                torch.cuda.synchronize()
+                osd = optimizer.state_dict()
+                osd["state"] = {i: {k: v.cpu() for k, v in st.items()} for i, st in osd["state"].items()}
+                payload = dict(format="cl_ica_amd.trainer", version=1, kind="supervised-autograd",
+                               f={k: v.detach().cpu().clone() for k, v in f.state_dict().items()}, optimizer=osd,
+                               step=int(optimizer.step_dev.item()))
+            payload["driver"] = dict(phase=_PHASE[supervised], phase_done=bool(done), global_step=int(global_step), losses=list(total_loss_values),
+                                     lin_scores=[float(v) for v in lin_scores], perm_scores=[float(v) for v in perm_scores],
+                                     spaces_state=dict(spaces._state), seed=int(seed), torch_rng_state=torch.get_rng_state(),
+                                     args={k: getattr(args, k) for k in _TRAJECTORY})
+            if rank == 0:
+                write_checkpoint(os.path.join(args.save_dir, f"{_PHASE[supervised]}_trainer.pth"), payload)
+
+        checkpointing = bool(args.checkpoint_every and args.save_dir)
         pending = []     # device scalars, fetched only at log time: no host sync per step
         applied0, first_step = (trainer.steps_done if fused else 0), global_step
         while global_step <= last_step:
@@ -243,6 +342,8 @@ def _main(argv=None):
                             "loss runs on the coordinate-difference sweeps for such steps")
             lin_scores.append(lin); perm_scores.append(perm)
             global_step += 1
+            if checkpointing and (global_step - 1) % args.checkpoint_every == 0 and global_step <= last_step:
+                checkpoint(False)
         if fused:
             # steps the guard withheld did not advance the device step counter: top the phase up to the number of APPLIED steps asked for
             want = last_step - first_step + 1
@@ -252,6 +353,9 @@ def _main(argv=None):
                 pending.append(trainer.step()[0].clone())
         if pending:
             total_loss_values += [float(v) for v in torch.stack(pending).cpu()]
+            pending = []
+        if checkpointing:
+            checkpoint(True)
         if fused and supervised:      # what the supervised phase ran on: part of the run's record (main()'s `supervised_engine`)
             st, ga = trainer.arith_state(), trainer.check_arith()
             supervised_engine = dict(arith=st.get("arith"), f16_flags=st.get("flags"), f16_steps_withheld=ga["skipped"],

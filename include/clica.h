@@ -185,6 +185,22 @@ int clica_lp_loss_train_spread(const clica_lp_loss_desc* d, const void* workspac
  * that fell back to the difference sweeps since the workspace was zeroed }.  Synchronises `stream`. */
 int clica_lp_loss_train_guard(const clica_lp_loss_desc* d, const void* workspace, size_t workspace_bytes, float* out4,
                               clica_stream_t stream);
+/* CHECKPOINTS: what ONE workspace carries from call to call ("keep ONE workspace per training loop" above), in portable form.  It is the
+ * guard / grid words of the matrix-core sweeps -- everything clica_lp_loss_train_guard and clica_lp_loss_train_spread report plus what the
+ * next call's prep launch reads: largest and last M, the violation word, the call id, the fallback count, max |x'| of the current and the
+ * next grid, the current / next / used origins.  The megabytes of planes, statistics and partials around them are rewritten by every
+ * call and the arrival counters are zero between calls: not state, so a restored workspace only has to be zero-filled and sized for `d`.
+ * The blob (device memory, 4-byte aligned, clica_lp_loss_train_state_bytes bytes) starts with a layout version word.
+ * export: one tiny launch; a desc whose calls run the VALU sweeps only (clica_lp_loss_train_path = 0) writes an all-zero blob.
+ * import: installs the words; an all-zero blob, or a desc whose shape never runs the matrix-core sweeps, is a no-op.  Reads the blob's first
+ * words back and synchronises `stream`.  After it the next clica_lp_loss_fwd_train call on the workspace takes the path and builds the
+ * planes it would have in the exporting process.  Call both between steps, outside a graph capture.  NULL, a short blob or another
+ * layout version: CLICA_E_INVALID before anything is launched. */
+int clica_lp_loss_train_state_bytes(size_t* bytes);
+int clica_lp_loss_train_state_export(const clica_lp_loss_desc* d, const void* workspace, size_t workspace_bytes, void* blob, size_t blob_bytes,
+                                     clica_stream_t stream);
+int clica_lp_loss_train_state_import(const clica_lp_loss_desc* d, void* workspace, size_t workspace_bytes, const void* blob, size_t blob_bytes,
+                                     clica_stream_t stream);
 /* Process-wide spread limit of the guard (M above which a call falls back); <= 0: back to CLICA_LP_MFMA_LIMIT / the default.  The limit is
  * a kernel ARGUMENT: a captured graph keeps the one it was captured with. */
 int clica_lp_loss_set_spread_limit(float limit);
@@ -461,6 +477,21 @@ int clica_split16_clear_flags(void* state, clica_stream_t stream);
 int clica_split16_guard(const void* state, int32_t* flags, int32_t* skipped, int32_t* updates, int32_t* poisoned, clica_stream_t stream);
 int clica_split16_set_dp_poison(void* state, const float* slot, clica_stream_t stream);
 int clica_split16_poison_export(const void* state, float* slot, clica_stream_t stream);
+/* CHECKPOINTS: the state in portable form.  A raw copy of `state` into another process is wrong -- it holds a device address
+ * (the data-parallel verdict slot) next to capacities and slot arrays -- so a step boundary is saved and restored through a BLOB of
+ * clica_split16_export_bytes bytes (device memory, 4-byte aligned): a layout version word, n_layers, the sticky flags, the number of
+ * updates (the generation), the guard's words (poison, gen_copy) and its count of withheld steps, and the scale arrays -- in force
+ * for activations, chain gradients, weights in forward and chain order, and those the last step ran with.
+ * clica_split16_export(state, n_layers, blob, blob_bytes): one tiny launch on `stream` that writes the blob.
+ * clica_split16_import(state, blob, blob_bytes, n_layers): installs the blob into an INITIALISED state (clica_split16_state_init, possibly
+ * used since): the verdict slot set by clica_split16_set_dp_poison and the capacities stay the importing process's, the live-slot counts
+ * and slot arrays go to their between-steps condition (empty).  After it the next training step on the state produces the bits it
+ * would have produced in the exporting process.  Call both between steps, outside a graph capture; the import reads the blob's first
+ * words back and synchronises `stream`.  NULL, n_layers outside 1..8, a blob shorter than clica_split16_export_bytes, another layout
+ * version or a blob exported with another n_layers: CLICA_E_INVALID before anything is launched. */
+int clica_split16_export_bytes(size_t* bytes);
+int clica_split16_export(const void* state, int32_t n_layers, void* blob, size_t blob_bytes, clica_stream_t stream);
+int clica_split16_import(void* state, const void* blob, size_t blob_bytes, int32_t n_layers, clica_stream_t stream);
 int clica_mlp_planes16_bytes(int64_t M, int32_t width, int32_t ones_column, size_t* bytes);
 int clica_mlp_pack_split16_bytes(int32_t n_layers, const int32_t* N, const int32_t* K, int32_t transpose, size_t* bytes);
 int clica_mlp_pack_split16_both(int32_t n_layers, const float* const* W, const int64_t* ldw, const int32_t* N, const int32_t* K,
