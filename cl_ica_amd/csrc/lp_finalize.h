@@ -24,6 +24,45 @@ __device__ __forceinline__ float pos_sum(const float* a, const float* b, int n, 
   return s;
 }
 
+
+// ---- the same on a row pair held in registers (the fused sweep's tile finisher: rows staged in LDS, at most W coordinates) ---------------
+// read_staged_row issues all W reads through an LDS-typed pointer (ds_read, not flat loads) before anything consumes them -- one wait
+// per row pair instead of one round trip per coordinate; the tail k >= n re-reads coordinate 0 and is masked in the arithmetic.
+// pos_sum_regs / grad_rows_regs pick the exponent kind ONCE, outside the coordinate loop, and keep pos_sum's / coef_row's expressions
+// and the summation order k = 0 .. n - 1: term and running sum stay a separate multiply and add, as in pos_sum (whose term comes out of
+// the exponent ladder and is never fused into the add; here `unfused` keeps the compiler from contracting the two) -- same bits.
+// Integer-exponent and generic kinds of p >= 1 only (no eps branch).
+__device__ __forceinline__ float unfused(float t) { asm("" : "+v"(t)); return t; }      // an opaque copy: no fma across it
+typedef const __attribute__((address_space(3))) float* lds_cfloat_ptr;
+template <int W>
+__device__ __forceinline__ void read_staged_row(float (&r)[W], const float* row, int n) {
+  lds_cfloat_ptr p = (lds_cfloat_ptr)row;
+#pragma unroll
+  for (int k = 0; k < W; ++k) r[k] = p[k < n ? k : 0];
+}
+template <int W>
+__device__ __forceinline__ float pos_sum_regs(const float (&a)[W], const float (&b)[W], int n, const Params& q) {
+  float s = 0.f;
+  if (q.p == 2.f) {
+#pragma unroll
+    for (int k = 0; k < W; ++k) { const float d = a[k] - b[k]; const float t = unfused(d * d); s = k < n ? s + t : s; }
+  } else if (q.p == 1.f) {
+#pragma unroll
+    for (int k = 0; k < W; ++k) { const float d = a[k] - b[k]; const float t = fabsf(d); s = k < n ? s + t : s; }
+  } else if (q.p == 3.f) {
+#pragma unroll
+    for (int k = 0; k < W; ++k) { const float d = a[k] - b[k]; const float t = unfused(fabsf(d) * d * d); s = k < n ? s + t : s; }
+  } else {
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      const float d = a[k] - b[k];
+      const float t = fabsf(d) > 0.f ? fexp2(q.p * flog2(fabsf(d))) : 0.f;
+      s = k < n ? s + t : s;
+    }
+  }
+  return s;
+}
+
 struct Means {
   float* blocksums;      // [gridDim.x][3] per-block partial sums
 };
@@ -56,6 +95,15 @@ constexpr int FIN_ROWS = 64;   // rows per finalize block; the 4 waves split the
 // sweep + the positive-pair gradient, upstream gradient = d(mean loss) = 1), saving the bwd_coef_k launch
 struct TrainOut { float* statL; float* statC; float* dz1; int64_t ldd1; float* dz2; int64_t ldd2; };
 
+// factor of d pos_i / d z in the positive pair's gradient rows (includes the factor p)
+__device__ __forceinline__ float cpos_of(const float sp_, const float A, const float C, const Params& q, float tau, int compat, const float L2) {
+  const float pos = q.pow ? sp_ : root_of<true>(sp_, q);
+  float cpos = A / tau;
+  if (compat) cpos -= (C / tau) * fexp2(-pos * q.kscale - L2);
+  cpos *= q.pow ? q.p : droot_of<true>(sp_, q);  // includes the factor p
+  return cpos;
+}
+
 // one row of the coefficient step (shared by bwd_coef_k and the training forward's finalize)
 __device__ __forceinline__ void coef_row(
     const int64_t i, const int64_t rows, const float* a /* row i of z1 */, const float* b /* row i of z2 */,
@@ -87,10 +135,7 @@ __device__ __forceinline__ void coef_row(
     return;
   }
   const float sp_ = pos_sum(a, b, q.n, q, frac != 0);
-  const float pos = q.pow ? sp_ : root_of<true>(sp_, q);
-  float cpos = A / tau;
-  if (compat) cpos -= (C / tau) * fexp2(-pos * q.kscale - L2);
-  cpos *= q.pow ? q.p : droot_of<true>(sp_, q);  // includes the factor p
+  const float cpos = cpos_of(sp_, A, C, q, tau, compat, L2);
   for (int k = 0; k < q.n; ++k) {
     const float d = a[k] - b[k];
     float dt;
@@ -111,6 +156,52 @@ __device__ __forceinline__ void coef_row(
   }
 }
 
+// coef_row for the fused sweep's tile finisher: Lp kind with p >= 1, upstream gradient d(mean loss) = 1, the row pair in registers and its
+// sum of powers `sp_` known from the loss (the same expression on the same values as coef_row's second pos_sum: computed once)
+template <int W>
+__device__ __forceinline__ void coef_row_regs(
+    const int64_t i, const int64_t rows, const float (&a)[W], const float (&b)[W], const float sp_,
+    const Params& q, float tau, float alpha, int compat, const float L2,
+    float* __restrict__ statL, float* __restrict__ statC,
+    float* __restrict__ dz1, int64_t ldd1, float* __restrict__ dz2, int64_t ldd2, float* statC_value) {
+  const float inv_rows = 1.f / (float)rows;
+  const float gi = 1.f * inv_rows + 0.f;
+  const float A = 2.f * alpha * gi + 0.f;
+  const float C = 2.f * (1.f - alpha) * gi + 0.f;
+  statL[i] = L2;
+  const float sc = q.xs * C / tau;
+  statC[i] = sc;
+  *statC_value = sc;
+  if (!dz1 && !dz2) return;
+  const float cpos = cpos_of(sp_, A, C, q, tau, compat, L2);
+  const int n = q.n;
+  auto put = [&](int k, float dt) {
+    const float g = cpos * dt;
+    if (k < n) {
+      if (dz1) dz1[i * ldd1 + k] = g;
+      if (dz2) dz2[i * ldd2 + k] = -g;
+    }
+  };
+  if (q.p == 2.f) {
+#pragma unroll
+    for (int k = 0; k < W; ++k) { const float d = a[k] - b[k]; put(k, d); }
+  } else if (q.p == 1.f) {
+#pragma unroll
+    for (int k = 0; k < W; ++k) { const float d = a[k] - b[k]; put(k, (d > 0.f ? 1.f : 0.f) - (d < 0.f ? 1.f : 0.f)); }
+  } else if (q.p == 3.f) {
+#pragma unroll
+    for (int k = 0; k < W; ++k) { const float d = a[k] - b[k]; put(k, d * fabsf(d)); }
+  } else {
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      const float d = a[k] - b[k];
+      const float ad = fabsf(d);
+      const float v = ad > 0.f ? fexp2((q.p - 1.f) * flog2(ad)) : 0.f;
+      put(k, d < 0.f ? -v : v);
+    }
+  }
+}
+
 
 // The per-row part of the finalize for block `blk` (FIN_ROWS rows, THREADS threads): merge of the per-split (max, sum) partials, the
 // positive pair, loss_i / pos_i / lse_i, and -- TrainOut -- the coefficient step.  Shared by fwd_finalize_k (its own launch) and by the
@@ -118,8 +209,10 @@ __device__ __forceinline__ void coef_row(
 // Scratch in LDS: sm, ss [THREADS / FIN_ROWS][FIN_ROWS]; zr0, zr1 [FIN_ROWS * zmaxn] (rows of z1 / z2 staged when n <= zmaxn);
 // ush [FIN_ROWS] or nullptr (u_i = C_i 2^-L_i for the caller's feature planes).  Returns through v_*: this thread's summands of the means.
 // COHERENT: the partials were written by other workgroups of THIS launch (agent-scope stores): read them with agent-scope loads.
+// W > 0 (the fused sweep: rows of at most W coordinates, always staged): the row pair is read from LDS into registers once and serves the
+// loss and the coefficient step (read_staged_row, pos_sum_regs, coef_row_regs); W = 0: any width, coordinates read as they are needed.
 struct FinScratch { float* sm; float* ss; float* zr0; float* zr1; int zmaxn; float* ush; };
-template <bool COHERENT = false>
+template <bool COHERENT = false, int W = 0>
 __device__ __forceinline__ void finalize_rows(
     const int blk, const float2* __restrict__ part, const int nsplit, const int64_t rows,
     const float* __restrict__ z1, int64_t ld1, const float* __restrict__ z2, int64_t ld2,
@@ -178,6 +271,11 @@ __device__ __forceinline__ void finalize_rows(
     float pos, xp;
     const float* ra = staged ? &S.zr0[lane_row * q.n] : z1 + i * ld1;
     const float* rb = staged ? &S.zr1[lane_row * q.n] : z2 + i * ld2;
+    const bool regs = W > 0 && staged && !dot && !frac;      // (the global fallback for n > zmaxn and the other kinds stay separate branches)
+    float av[W > 0 ? W : 1], bv[W > 0 ? W : 1], sp_regs = 0.f;
+    if constexpr (W > 0) {
+      if (regs) { read_staged_row<W>(av, &S.zr0[lane_row * q.n], q.n); read_staged_row<W>(bv, &S.zr1[lane_row * q.n], q.n); }
+    }
     if (dot) {   // SimCLRLoss: pos = <z1, z2> and the logit is +pos/tau (losses.py:188-193)
       pos = 0.f;
       if (q.posdot) pos = q.posdot[i];
@@ -185,7 +283,10 @@ __device__ __forceinline__ void finalize_rows(
       xp = pos * q.kscale;
       pos = -pos;  // loss_pos = -pos/tau (losses.py:192)
     } else {
-      const float sp_ = pos_sum(ra, rb, q.n, q, frac != 0);
+      float sp_;
+      if constexpr (W > 0) sp_ = regs ? pos_sum_regs<W>(av, bv, q.n, q) : pos_sum(ra, rb, q.n, q, frac != 0);
+      else sp_ = pos_sum(ra, rb, q.n, q, frac != 0);
+      sp_regs = sp_;
       pos = q.pow ? sp_ : root_of<true>(sp_, q);
       xp = -pos * q.kscale;
     }
@@ -201,9 +302,15 @@ __device__ __forceinline__ void finalize_rows(
     const float li = 2.f * (alpha * lp + (1.f - alpha) * lse);
     loss_i[i] = li; pos_i[i] = lp; lse_i[i] = L2;
     float sc_i = 0.f;
-    if (T.statL)
-      coef_row(i, rows, ra, rb, q, tau, alpha, compat, frac, dot, L2, nullptr, nullptr, nullptr, nullptr, T.statL, T.statC,
-               T.dz1, T.ldd1, T.dz2, T.ldd2, &sc_i);
+    if (T.statL) {
+      bool done = false;
+      if constexpr (W > 0) {
+        if (regs) { coef_row_regs<W>(i, rows, av, bv, sp_regs, q, tau, alpha, compat, L2, T.statL, T.statC, T.dz1, T.ldd1, T.dz2, T.ldd2, &sc_i); done = true; }
+      }
+      if (!done)
+        coef_row(i, rows, ra, rb, q, tau, alpha, compat, frac, dot, L2, nullptr, nullptr, nullptr, nullptr, T.statL, T.statC,
+                 T.dz1, T.ldd1, T.dz2, T.ldd2, &sc_i);
+    }
     v_loss = li; v_pos = lp; v_lse = lse;
     if (S.ush) S.ush[lane_row] = sc_i * fexp2(-L2);            // u_i = C_i 2^-L_i (the value coef_row has just stored in statC[i])
   } else if (S.ush && grp == 0) {
@@ -248,14 +355,17 @@ __global__ __launch_bounds__(THREADS, fwd_min_waves(NP, false)) void fwd_partial
     if (s_last) __hip_atomic_store(&F.arrive[blockIdx.x], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // all arrivals of this launch are in
   }
   __syncthreads();
-  if (!s_last) return;
+  LPT_STAMP(4);
+  if (!s_last) { LPT_FLUSH(0); return; }
   float v_loss, v_pos, v_lse;
   constexpr int ZMAXN = 2 * tile_rows(NP) * NP / (2 * FIN_ROWS);      // floats per staged row the tile buffers hold for z1 and z2 each
   static_assert(ZMAXN >= NP, "tile buffers too small for the z rows");
-  finalize_rows<true>((int)blockIdx.x, part, (int)gridDim.y, n_own, own, ldo, F.z2, F.ld2, q, F.tau, F.alpha, F.compat, 0, 0, F.log_b3,
+  finalize_rows<true, NP>((int)blockIdx.x, part, (int)gridDim.y, n_own, own, ldo, F.z2, F.ld2, q, F.tau, F.alpha, F.compat, 0, 0, F.log_b3,
                 F.loss_i, F.pos_i, F.lse_i, F.T, FinScratch{&sm[0][0], &ss[0][0], scratch, scratch + FIN_ROWS * ZMAXN, ZMAXN, nullptr},
                 v_loss, v_pos, v_lse);
   reduce_means(v_loss, v_pos, v_lse, F.M, (int)blockIdx.x, /*coherent=*/F.means != nullptr);
+  LPT_STAMP(5);
+  LPT_FLUSH(0);
   if (!F.means) return;
   // second level: the last tile finisher sums all block sums (they were agent-scope stores of threads 0..2; wait for their acknowledgement)
   __builtin_amdgcn_s_waitcnt(0x0F70);

@@ -45,8 +45,10 @@ constexpr int jb_fwd(int np) { return np <= 16 ? 4 : 2; }
 constexpr int JBW = CLICA_LP_JBW;   // the same for the backward sweep (RPP = 16 rows per partition and tile: 2, 4, 8 or 16)
 // stream rows per LDS tile: every partition gets TS / PARTS of them (32 / 16 / 8 rows)
 #ifndef CLICA_LP_TS16
-#define CLICA_LP_TS16 128      // measured (tools/loss_train_probe.py): 128 beats 256 by 14 % on the backward sweep (registers: the
-#endif                        // staging prefetch holds TS NP / 256 values per thread across the tile's arithmetic)
+#define CLICA_LP_TS16 128      // measured (tools/loss_train_probe.py): 128 beat 256 by 14 % on the backward sweep (registers: the
+#endif                        // staging prefetch holds TS NP / 256 values per thread across the tile's arithmetic) -- while the prefetch was
+                              // still waited for at the tile's head.  Without that wait 256 is 0.4 us ahead on either headline sweep
+                              // (profiles/lp_tile_prefetch_ab.md); not switched: the suite has not run at 256
 #ifndef CLICA_LP_TS40
 #define CLICA_LP_TS40 128
 #endif
@@ -180,28 +182,74 @@ __device__ __forceinline__ float droot_of(float s, const Params& q) {
 }
 
 // ---- staging -----------------------------------------------------------------------------
-// Global -> registers -> LDS, split in two so the global loads of tile t+1 are in flight while tile t
-// is being consumed (double-buffered LDS, one barrier per tile).  Branch-free: masked-out elements
-// read element 0 and are zeroed by a select at store time.
+// Global -> registers -> LDS, split in two so the global loads of tile t+1 are in flight while tile t is being consumed
+// (double-buffered LDS, one barrier per tile).  load() only ISSUES the loads and keeps the raw words: nothing reads them before
+// store(), behind the tile's pair loop, where the coordinate scale `pre` and the zero of the masked elements (padding columns k >= n,
+// rows past a ragged tile's end) are applied -- the same fp32 multiply and select on the same words as before, so the first wait on
+// these registers sits behind the tile's arithmetic, not in front of it.
+// Addresses: the tiles of a chunk are loaded in order, so the stager walks a wave-uniform pointer (+ TS rows per tile) and adds a
+// per-thread byte offset per element that is computed once (row * ld + k, or 0 for a padding column: the tile's first word is always
+// readable).  Full tiles (all but a ragged last one) take a path without per-row predicates.  Branch-free inside each path: masked-out
+// elements read the tile's first word.  A leading dimension whose tile does not fit 32-bit byte offsets (> 4 M floats) is served
+// without prefetch: store() reads the tile itself, with 64-bit indexing per element.
 template <int NP>
 struct Stager {
   static constexpr int TS = tile_rows(NP);
   static constexpr int ITERS = TS * NP / THREADS;
   static_assert((TS * NP) % THREADS == 0, "tile must divide over the workgroup");
-  float v[ITERS];
-  __device__ __forceinline__ void load(const float* __restrict__ str, int64_t lds, int64_t j0, int cnt, int n, float pre = 1.f) {
+  float v[ITERS];            // raw words of the tile in flight
+  unsigned off[ITERS];       // byte offset of element `it` inside a tile; 0 for a padding column
+  bool kok[ITERS];           // k < n (loop-invariant)
+  const float* base;         // first row of the tile the next load() reads
+  int64_t ld;
+  int cnt;                   // rows of the tile held in v[]
+  int nn;                    // true row width
+  bool wide;                 // a tile spans more than 32-bit byte offsets
+  __device__ __forceinline__ void init(const float* __restrict__ str, int64_t lds, int64_t j0, int n) {
+    base = str + j0 * lds; ld = lds; cnt = 0; nn = n;
+    wide = lds > (int64_t)(0x7fffffff / (4 * TS));
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
       const int idx = threadIdx.x + it * THREADS;
       const int row = idx / NP, k = idx - row * NP;
-      const bool ok = row < cnt && k < n;
-      const float x = str[ok ? (j0 + row) * lds + k : 0];
-      v[it] = ok ? x * pre : 0.f;
+      kok[it] = k < n;
+      off[it] = kok[it] ? ((unsigned)row * (unsigned)lds + (unsigned)k) * 4u : 0u;
     }
   }
-  __device__ __forceinline__ void store(float* tile) const {
+  // issue the loads of the next tile (`c` rows of it exist) and step to the one after
+  __device__ __forceinline__ void load(int c) {
+    const char* b = reinterpret_cast<const char*>(base);
+    cnt = c;
+    if (!wide) {
+      if (c == TS) {
 #pragma unroll
-    for (int it = 0; it < ITERS; ++it) tile[threadIdx.x + it * THREADS] = v[it];
+        for (int it = 0; it < ITERS; ++it) v[it] = *reinterpret_cast<const float*>(b + off[it]);
+      } else {
+        const unsigned end = (unsigned)c * (unsigned)ld * 4u;      // row < c  <=>  off < c ld 4 (k < n <= ld; padding columns sit at 0)
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it) v[it] = *reinterpret_cast<const float*>(b + (off[it] < end ? off[it] : 0u));
+      }
+    }
+    base += (int64_t)TS * ld;
+  }
+  __device__ __forceinline__ void store(float* tile, float pre = 1.f) const {
+    if (wide) {      // no prefetch: the tile is read here, with 64-bit indexing per element (rolled: nothing of it is kept across the tile)
+      const float* b = base - (int64_t)TS * ld;
+#pragma unroll 1
+      for (int idx = threadIdx.x; idx < TS * NP; idx += THREADS) {
+        const int row = idx / NP, k = idx - row * NP;
+        const bool ok = k < nn && row < cnt;
+        const float x = b[ok ? (int64_t)row * ld + k : 0];
+        tile[idx] = ok ? x * pre : 0.f;
+      }
+    } else if (cnt == TS) {
+#pragma unroll
+      for (int it = 0; it < ITERS; ++it) tile[threadIdx.x + it * THREADS] = kok[it] ? v[it] * pre : 0.f;
+    } else {
+      const unsigned end = (unsigned)cnt * (unsigned)ld * 4u;
+#pragma unroll
+      for (int it = 0; it < ITERS; ++it) tile[threadIdx.x + it * THREADS] = (kok[it] && off[it] < end) ? v[it] * pre : 0.f;
+    }
   }
 };
 
@@ -293,6 +341,29 @@ __device__ __forceinline__ void gaccum2_d(f32x2& g, float coef, f32x2 d) {
   }
 }
 
+// ---- phase trace, debug build only (-DCLICA_LP_TRACE on lp_loss_pk.hip: `make lptrace`, tools/lp_trace.py) ------------------------------
+// Thread 0 of every workgroup stamps the clock at the points below into LDS and writes the stamps (vector stores) to the debug buffer
+// when the workgroup leaves: [kind: 0 forward, 1 backward][workgroup, < LPT_MAXWG][LPT_NS].  The product build carries none of it.
+//   0 entry   1 owner loads issued   2 first tile staged (barrier passed)   3 merge done   4 arrival   5 finisher done   6 exit
+//   LPT_HEAD + 4 t + {0 loads of tile t + 1 issued, 1 pair loop entered, 2 pair loop left, 3 store + barrier passed}, t < LPT_MAXT
+#ifdef CLICA_LP_TRACE
+static __device__ unsigned long long* g_lp_trace = nullptr;
+constexpr int LPT_MAXWG = 1024, LPT_MAXT = 8, LPT_HEAD = 8, LPT_NS = LPT_HEAD + 4 * LPT_MAXT;
+__device__ __forceinline__ unsigned long long* lpt_buf() { __shared__ unsigned long long b[LPT_NS]; return b; }
+#define LPT_INIT() do { if (threadIdx.x == 0) { for (int i_ = 0; i_ < LPT_NS; ++i_) lpt_buf()[i_] = 0; lpt_buf()[0] = __builtin_readcyclecounter(); } } while (0)
+#define LPT_STAMP(slot) do { if (threadIdx.x == 0) lpt_buf()[slot] = __builtin_readcyclecounter(); } while (0)
+#define LPT_TILE(t, ph) do { if (threadIdx.x == 0 && (t) < LPT_MAXT) lpt_buf()[LPT_HEAD + 4 * (t) + (ph)] = __builtin_readcyclecounter(); } while (0)
+#define LPT_FLUSH(kind) do { if (threadIdx.x == 0 && g_lp_trace) { \
+    const unsigned wg_ = blockIdx.y * gridDim.x + blockIdx.x; \
+    lpt_buf()[6] = __builtin_readcyclecounter(); \
+    if (wg_ < (unsigned)LPT_MAXWG) for (int i_ = 0; i_ < LPT_NS; ++i_) g_lp_trace[((size_t)(kind) * LPT_MAXWG + wg_) * LPT_NS + i_] = lpt_buf()[i_]; } } while (0)
+#else
+#define LPT_INIT() do { } while (0)
+#define LPT_STAMP(slot) do { } while (0)
+#define LPT_TILE(t, ph) do { } while (0)
+#define LPT_FLUSH(kind) do { } while (0)
+#endif
+
 // ---- forward: per-split (max, sum) partials in the log2 domain -----------------------------
 // ROWGRAD: also accumulate G_k = sum_j 2^(x_ij - m) * p * droot * (1/p) d term / d owner_k with the same
 // running-max rescaling (the flash-attention forward with "V" = the pair's distance derivative).  After
@@ -321,7 +392,9 @@ __device__ __forceinline__ void fwd_partial_body(
   const int64_t own0 = (int64_t)bx * (HALF * R);
   f32x2 o[R][NP / 2];
   f32x2 G[ROWGRAD ? R : 1][NP / 2];
+  LPT_INIT();
   load_owners<NP, R>(o, own, ldo, own0, n_own, q.n, q.pre);
+  LPT_STAMP(1);
   float m[R], s[R];
   const float csgn = (PK == 0) ? q.sgn : 1.f;
 #pragma unroll
@@ -337,15 +410,18 @@ __device__ __forceinline__ void fwd_partial_body(
   const int64_t je = min(n_str, jb + (int64_t)chunk);
   Stager<NP> st;
   if (jb < je) {
-    st.load(str, lds, jb, (int)min((int64_t)TS, je - jb), q.n, q.pre);
-    st.store(tiles[0]);
+    st.init(str, lds, jb, q.n);
+    st.load((int)min((int64_t)TS, je - jb));
+    st.store(tiles[0], q.pre);
   }
   __syncthreads();
+  LPT_STAMP(2);
   int cur = 0;
   for (int64_t j0 = jb; j0 < je; j0 += TS, cur ^= 1) {
     const int cnt = (int)min((int64_t)TS, je - j0);
     const bool more = j0 + TS < je;
-    if (more) st.load(str, lds, j0 + TS, (int)min((int64_t)TS, je - j0 - TS), q.n, q.pre);   // in flight during the tile
+    if (more) st.load((int)min((int64_t)TS, je - j0 - TS));   // issued here, first read by the store behind the pair loop
+    LPT_TILE((int)((j0 - jb) / TS), 0);
     const float* tile = tiles[cur] + pq * RPP * NP;
     const int cq = min(RPP, max(0, cnt - pq * RPP));    // valid rows of this partition (ragged last tile only)
     // full partitions (every tile but a ragged last one) skip the per-row tail mask: same values, two instructions fewer per pair
@@ -399,9 +475,12 @@ __device__ __forceinline__ void fwd_partial_body(
       }
     }
     };
+    LPT_TILE((int)((j0 - jb) / TS), 1);
     if (cq == RPP) sweep(std::false_type{}); else sweep(std::true_type{});
-    if (more) st.store(tiles[cur ^ 1]);     // last read one iteration ago, behind the previous barrier
+    LPT_TILE((int)((j0 - jb) / TS), 2);
+    if (more) st.store(tiles[cur ^ 1], q.pre);     // last read one iteration ago, behind the previous barrier
     __syncthreads();
+    LPT_TILE((int)((j0 - jb) / TS), 3);
   }
   // ---- merge the workgroup's eight partitions on chip: half-waves by shuffle, waves through LDS (fixed order) ----
   float* gred = &tiles[0][0];               // [WAVES][HALF * R][NP]; every wave is past its last tile read (barrier above)
@@ -467,6 +546,8 @@ __device__ __forceinline__ void fwd_partial_body(
       }
     }
   }
+  LPT_STAMP(3);
+  if (!scratch_out) LPT_FLUSH(0);      // (the fused form goes on: fwd_partial_fin_k writes the stamps)
 }
 
 template <int NP, int PK, int R, bool ROOT, bool ROWGRAD, int NQ = NP / 2, bool ZMAX = false>
@@ -501,7 +582,9 @@ __device__ __forceinline__ void bwd_pairs_body(
   const int pq = wave * 2 + hf;
   const int64_t own0 = (int64_t)bx * (HALF * R);
   f32x2 o[R][NP / 2], g[R][NP / 2];
+  LPT_INIT();
   load_owners<NP, R>(o, own, ldo, own0, n_own, q.n, q.pre);
+  LPT_STAMP(1);
   float oL[R], oC[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
@@ -517,32 +600,37 @@ __device__ __forceinline__ void bwd_pairs_body(
   const int64_t jb = (int64_t)by * chunk;
   const int64_t je = min(n_str, jb + (int64_t)chunk);
   Stager<NP> st;
-  float rl = 0.f, rc = 0.f;     // staged stream statistics (threads < TS)
+  float rl = 0.f, rc = 0.f;     // staged stream statistics (threads < TS): raw words, like the Stager's, until store_stats
   auto load_stats = [&](int64_t j0, int cnt) {
     if (STREAM_STATS && (int)threadIdx.x < TS) {
       const bool ok = (int)threadIdx.x < cnt;
-      const float l = strL[ok ? j0 + threadIdx.x : 0], c = strC[ok ? j0 + threadIdx.x : 0];
-      rl = ok ? l : 0.f;
-      rc = ok ? c : 0.f;         // zero coefficient masks the ragged tail
+      rl = strL[ok ? j0 + threadIdx.x : 0]; rc = strC[ok ? j0 + threadIdx.x : 0];
     }
   };
-  auto store_stats = [&](int b) {
-    if (STREAM_STATS && (int)threadIdx.x < TS) { tLs[b][threadIdx.x] = rl; tCs[b][threadIdx.x] = FOLD ? rc * fexp2(-rl) * q.gfold : rc; }
+  auto store_stats = [&](int b) {      // (st.cnt: the rows of the tile being stored)
+    if (STREAM_STATS && (int)threadIdx.x < TS) {
+      const bool ok = (int)threadIdx.x < st.cnt;
+      const float l = ok ? rl : 0.f, c = ok ? rc : 0.f;         // zero coefficient masks the ragged tail
+      tLs[b][threadIdx.x] = l; tCs[b][threadIdx.x] = FOLD ? c * fexp2(-l) * q.gfold : c;
+    }
   };
   if (jb < je) {
     const int c0 = (int)min((int64_t)TS, je - jb);
-    st.load(str, lds, jb, c0, q.n, q.pre); load_stats(jb, c0);
-    st.store(tiles[0]); store_stats(0);
+    st.init(str, lds, jb, q.n);
+    st.load(c0); load_stats(jb, c0);
+    st.store(tiles[0], q.pre); store_stats(0);
   }
   __syncthreads();
+  LPT_STAMP(2);
   int cur = 0;
   for (int64_t j0 = jb; j0 < je; j0 += TS, cur ^= 1) {
     const int cnt = (int)min((int64_t)TS, je - j0);
     const bool more = j0 + TS < je;
     if (more) {
       const int c1 = (int)min((int64_t)TS, je - j0 - TS);
-      st.load(str, lds, j0 + TS, c1, q.n, q.pre); load_stats(j0 + TS, c1);
+      st.load(c1); load_stats(j0 + TS, c1);
     }
+    LPT_TILE((int)((j0 - jb) / TS), 0);
     const float* tile = tiles[cur] + pq * RPP * NP;
     const float* tL = tLs[cur] + pq * RPP;
     const float* tC = tCs[cur] + pq * RPP;
@@ -556,6 +644,7 @@ __device__ __forceinline__ void bwd_pairs_body(
     // more than the second pair in flight hid
     constexpr bool KEEPD = PK >= 1 && PK <= 3 && (NP <= 16 || (CLICA_LP_KEEPD_WIDE && NP <= 40));
     constexpr int JW = KEEPD ? 1 : JBW;      // (narrow rows with kept differences: 1 / 2 / 4 pairs in flight = 50.5 / 51.2 / 57.8 us at n = 10)
+    LPT_TILE((int)((j0 - jb) / TS), 1);
     for (int jj = 0; jj < cq; jj += JW) {
 #pragma unroll
       for (int r = 0; r < R; ++r) {
@@ -603,8 +692,10 @@ __device__ __forceinline__ void bwd_pairs_body(
         }
       }
     }
-    if (more) { st.store(tiles[cur ^ 1]); store_stats(cur ^ 1); }
+    LPT_TILE((int)((j0 - jb) / TS), 2);
+    if (more) { st.store(tiles[cur ^ 1], q.pre); store_stats(cur ^ 1); }
     __syncthreads();
+    LPT_TILE((int)((j0 - jb) / TS), 3);
   }
   // ---- sum the eight partitions on chip (fixed order: lower half + upper half, then waves 0..3) ----
   float* gred = &tiles[0][0];               // [WAVES][HALF * R][NP]
@@ -637,6 +728,8 @@ __device__ __forceinline__ void bwd_pairs_body(
     }
     *reinterpret_cast<float4*>(part + ((int64_t)by * n_own + i) * NP + 4 * k4) = a4;
   }
+  LPT_STAMP(3);
+  LPT_FLUSH(1);
 }
 
 template <int NP, int PK, int R, int STATS, bool ROOT, int NQ = NP / 2, bool FOLD = false>
@@ -797,9 +890,11 @@ struct Plan {
   int64_t tiles;  // owner tiles (32 R owners each)
   int nsplit, chunk;
 };
+int max_splits_cap();      // clica_set_tuning("lp_max_splits", k): at most k HBM-level stream splits (0 = no cap, the default); lp_loss.hip
 inline Plan make_plan(int64_t n_own, int64_t n_str, int n, bool bwd, int resident = 0) {
   Plan P;
   P.np = pad_dim(n);
+  const int64_t cap_ns = max_splits_cap();      // test hook: with few splits a small pool is several LDS tiles per workgroup
   if (P.np > 64) {          // wide rows: 16 owners per workgroup, about four workgroups per CU, splits in whole LDS tiles
     const int64_t TSW = wide_ts(wide_kc(n));
     P.R = 0;
@@ -807,6 +902,7 @@ inline Plan make_plan(int64_t n_own, int64_t n_str, int n, bool bwd, int residen
     int64_t ns = ceil_div((int64_t)kNumCU * 4, P.tiles);
     const int64_t cap = ceil_div(n_str, TSW);
     if (ns > cap) ns = cap;
+    if (cap_ns > 0 && ns > cap_ns) ns = cap_ns;
     if (ns < 1) ns = 1;
     const int64_t chunk = ceil_div(ceil_div(n_str, ns), TSW) * TSW;
     P.chunk = (int)chunk;
@@ -821,6 +917,7 @@ inline Plan make_plan(int64_t n_own, int64_t n_str, int n, bool bwd, int residen
   // = exactly 3 workgroups per CU; the 8-rank pool (B3 = 49 152): 96 x 24 splits of 2048 rows = three rounds of that.
   const int64_t max_split = ceil_div(n_str, TS);
   auto finish = [&](int64_t ns) {
+    if (cap_ns > 0 && ns > cap_ns) ns = cap_ns;
     if (ns < 1) ns = 1;
     if (ns > max_split) ns = max_split;
     int64_t chunk = ceil_div(ceil_div(n_str, ns), TS) * TS;

@@ -302,6 +302,14 @@ extern "C" int clica_lp_loss_workspace_bytes(const clica_lp_loss_desc* d, size_t
 // clica_set_tuning("lp_fused_finalize", 0): the forwards as sweep + fwd_finalize_k (+ means_k) launches (test / A-B hook -- same bits)
 static int& fused_finalize_switch() { static int on = 1; return on; }
 namespace clica { namespace lp { void set_fused_finalize(int on) { fused_finalize_switch() = on ? 1 : 0; } } }       // clica_set_tuning (linear.hip)
+// clica_set_tuning("lp_max_splits", k): make_plan (lp_kernels.h) cuts the stream into at most k HBM-level splits, for the launches and the
+// workspace sizes alike (both come from make_plan).  Test hook: the product plan gives a workgroup more than one LDS tile only from
+// B ~ 2500 on; with k = 1 a pool of a few hundred rows runs the tile loop's prefetch and a ragged last tile.  0 = no cap (the default).
+static int& max_splits_switch() { static int cap = 0; return cap; }
+namespace clica { namespace lp {
+void set_max_splits(int k) { max_splits_switch() = k > 0 ? k : 0; }       // clica_set_tuning (linear.hip)
+int max_splits_cap() { return max_splits_switch(); }
+} }
 static bool launch_fwd_partial_fin(const Plan& P, int pk, const float* own, int64_t ldo, int64_t n_own, const float* str, int64_t lds,
                                    int64_t n_str, const Params& q, float2* part, const FinArgs& F, hipStream_t st) {
   switch (pk) {

@@ -152,3 +152,9 @@ void CAT(launch_bwd_sym_pk, CLICA_PK)(const Plan& P, const float* own, int64_t l
 
 }  // namespace lp
 }  // namespace clica
+
+#ifdef CLICA_LP_TRACE      // tools/lp_trace.py: the debug buffer of this translation unit's sweeps (lp_kernels.h: LPT_*), NULL = off
+extern "C" int clica_debug_lp_trace(unsigned long long* buf) {
+  return (int)hipMemcpyToSymbol(HIP_SYMBOL(clica::lp::g_lp_trace), &buf, sizeof(buf));
+}
+#endif

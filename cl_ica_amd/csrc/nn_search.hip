@@ -53,7 +53,8 @@ __global__ __launch_bounds__(THREADS) void nn_partial_k(const float* __restrict_
   const int64_t je = min(n_tab, jb + (int64_t)chunk);
   Stager<NP> st;
   if (jb < je) {
-    st.load(tab, ldt, jb, (int)min((int64_t)TS, je - jb), q.n);
+    st.init(tab, ldt, jb, q.n);
+    st.load((int)min((int64_t)TS, je - jb));
     st.store(tiles[0]);
   }
   __syncthreads();
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(THREADS) void nn_partial_k(const float* __restrict_
   for (int64_t j0 = jb; j0 < je; j0 += TS, cur ^= 1) {
     const int cnt = (int)min((int64_t)TS, je - j0);
     const bool more = j0 + TS < je;
-    if (more) st.load(tab, ldt, j0 + TS, (int)min((int64_t)TS, je - j0 - TS), q.n);
+    if (more) st.load((int)min((int64_t)TS, je - j0 - TS));
     const float* tile = tiles[cur] + pq * RPP * NP;
     const int cq = min(RPP, max(0, cnt - pq * RPP));
     const int row0 = (int)j0 + pq * RPP;

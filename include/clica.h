@@ -42,7 +42,9 @@ const char* clica_last_error(void);
  * template instead of the vector-ALU kernels for tiny K / N), "gemm_cfg_fwd" / "gemm_cfg_dgrad" / "gemm_cfg_wgrad" (tile configuration id,
  * -1: by shape), "dot_mfma" (0: SimCLRLoss pair sweep at every width), "gemm16_epilogue" (0: clica_linear_split_fwd16 / _dgrad16 keep the
  * generic fused epilogue instead of the one specialised per output combination), "lp_fused_finalize" (0: clica_lp_loss_fwd_train as sweep +
- * finalize launch), "reset" (all defaults).  Unknown key: CLICA_E_INVALID.  The library
+ * finalize launch), "lp_max_splits" (k > 0: the Lp / dot loss sweeps and clica_nn_search cut their stream into at most k splits, in the
+ * launches and in the workspace sizes alike -- set it before the workspace query; with k = 1 a pool of a few hundred rows is several
+ * on-chip tiles per workgroup, which the product plan only reaches from B ~ 2500 on; 0: no cap, the default), "reset" (all defaults).  Unknown key: CLICA_E_INVALID.  The library
  * reads NO tuning switch from the environment (the environment variables it does read are listed in INTEGRATION.md). */
 int clica_set_tuning(const char* key, int32_t value);
 /* After a FAILED stream capture on `stream` (e.g. a collective that cannot be captured): end the capture if the stream is
