@@ -62,10 +62,52 @@ def _abort_capture(graph, stream, others=()) -> None:
         lib.clica_abort_capture(C.c_void_p(st.cuda_stream))
 
 
-class ContrastiveTrainer:
+class StepHandoffs:
+    """What one piece of a step leaves for a later piece of the SAME step (a misspelt field raises).  Idle between steps; a piece called
+    outside _step_body finds every fold off.  field: written by -> consumed by
+        in_step        _step_body, around loss / backward  -> loss_forward_backward: may the objective be left to the backward chain?
+        fold_adam      _step_body, behind the loss         -> backward_chain (tail), weight_grads (Adam in the slab reduction)
+        ticked         loss_forward_backward               -> weight_grads (Adam's t), optimizer_step (clears it; ticks if unset)
+        adam_done      weight_grads                        -> optimizer_step (clears it; nothing left to launch)
+        tail_ready     backward_chain                      -> weight_grads (clears it; the n-wide layers' slabs are in the workspace)
+        scales_updated optimizer_step                      -> _step_body (did the Adam launch update the f16x2 scales?)
+        dy_parts       ContrastiveTrainer.loss_forward_backward -> backward_chain (clears it; dy still lacks the sweep's partials)
+        mse            SupervisedTrainer.loss_forward_backward  -> backward_chain (clears it; the chain's prologue forms dY and the loss)"""
+    IDLE = dict(in_step=False, fold_adam=False, ticked=False, adam_done=False, tail_ready=False, scales_updated=False,
+                dy_parts=None, mse=None)
+    __slots__ = tuple(IDLE)
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self, *fields):
+        """Back to idle: every field (load_state_dict), or only the named ones (the end of a step, a calibration pass)."""
+        for name in fields or self.IDLE:
+            setattr(self, name, self.IDLE[name])
+
+
+@dataclass(frozen=True)
+class StepPlan:
+    """The launch structure of a step inside _step_body, fixed by what the trainer was constructed with (the class-attribute test
+    hooks included: they are read once, at the end of construction)."""
+    adam_in_wgrad: bool        # the weight gradients' slab reduction applies Adam as well
+    chain_tail: bool           # the backward chain leaves the n-wide layers' weight-gradient slabs (needs adam_in_wgrad)
+    dy_from_partials: bool     # ... and its prologue finishes dy from the loss sweep's partials (contrastive, p >= 1)
+    mse_in_chain: bool         # ... or forms the MSE objective (supervised)
+    guard_rides: bool          # data parallel: the f16x2 guard's verdict rides in the first gradient bucket
+    wgrad_halves: bool         # data parallel: the grouped weight gradients go out in two halves
+
+
+class _FusedTrainer:
+    """What the contrastive and the supervised step share: the encoder paths, arenas, sampler and mixing net, pack, forward, heads,
+    backward chain, weight gradients, optimizer, calibration and guard bookkeeping of the f16x2 arithmetic, checkpoints, capture and
+    step / step_injected.  A subclass brings the objective: _enc_rows, _allocate_loss, loss_forward_backward, _objective_folds,
+    _result, inject, plan_summary and what its loss carries into a checkpoint."""
+    p = tau = alpha = None           # (the contrastive objective's; checkpoints carry them as None otherwise)
+    keep_fp32_copies = False         # (inspection, set on the class before construction: the split path also writes every fp32 copy)
+
     def __init__(self, f: nn.Sequential, g_weights: torch.Tensor, sampler: SamplerSpec, batch_size: int,
-                 p: float = 2, tau: float = 1.0, alpha: float = 0.5, lr: float = 1e-4, g_slope: float = 0.2,
-                 betas=(0.9, 0.999), eps: float = 1e-8, device=None,
+                 lr: float = 1e-4, g_slope: float = 0.2, betas=(0.9, 0.999), eps: float = 1e-8, device=None,
                  process_group: Optional[dist.ProcessGroup] = None, bucket_bytes: int = 8 << 20,
                  force_collectives: bool = False, overlap_backward: bool = True, fused_forward: bool = True,
                  split_bf16: Optional[bool] = None, g_act_kind: int = 0, emulate_pool_ranks: int = 1, dry_ranks: int = 1,
@@ -75,7 +117,6 @@ class ContrastiveTrainer:
         self.B = int(batch_size)
         self.n = sampler.n
         self.sampler = sampler
-        self.p, self.tau, self.alpha = float(p), float(tau), float(alpha)
         self.lr, self.betas, self.eps = float(lr), betas, float(eps)
         self.g_slope = float(g_slope)
         self.g_act_kind = int(g_act_kind)     # hidden activation of g (ops.MIX_ACT); the fused prologue handles LeakyReLU / ReLU only
@@ -101,9 +142,16 @@ class ContrastiveTrainer:
         self.dry_ranks = int(dry_ranks) if (self.world == 1 and self.dp) else 1
         if int(dry_ranks) > 1 and self.dry_ranks == 1:
             raise ValueError("dry_ranks needs an initialised one-rank process group and force_collectives=True")
-        # p = 0: SimCLRLoss(normalize=False, tau, alpha) -- InfoNCE on dot products (losses.py:162-202), the objective of the
-        # reference's hypersphere experiment; the loss runs on the dot kind's training pair (csrc/dot_train.hip)
-        self.dot = self.p == 0
+        self.handoff = StepHandoffs()
+        self.stamps = None                     # bench.py: device time stamps around the encoder launches, valid inside the graph
+        self._dy_parts_taken = self._mse_taken = 0      # (tests: how many steps left their objective to the backward chain)
+        self._planes_on_current_scales = False
+        # the marginal's mean (main_mlp.py:148-150: the first unit vector on the sphere)
+        self._eta = None
+        if sampler.marginal != "uniform":
+            self._eta = torch.zeros(1, self.n, device=self.device)
+            if sampler.space == "sphere":
+                self._eta[0, 0] = 1.0
 
         mods = list(self.f)
         for idx, m in enumerate(mods):
@@ -187,6 +235,27 @@ class ContrastiveTrainer:
                 self._guard_rides = False
         self.buckets = GradBuckets(self._grad_buf if self._guard_rides else self.grad_arena, slices, self.world, process_group, bucket_bytes,
                                    force=self.dp, boundaries=(L - 1 - self._half,) if self.wgrad_halves else ()) if self.dp else None
+        self.plan = self._plan_step()
+
+    # Test hook (class attribute, tests/test_gpu_engine.py): both the folded and the unfolded launch structures are product paths -- the
+    # unfolded ones run under data parallelism and behind a head -- and the equivalence tests compare them on ONE trainer configuration.
+    chain_tail = True            # the backward chain's tail writes the n-wide layers' weight-gradient slabs (clica_mlp_dgrad_split_tail)
+
+    def _plan_step(self) -> StepPlan:
+        """Decided once, when everything the decisions depend on is constructed (StepPlan)."""
+        # The optimizer can ride in the weight-gradient reduction when ONE whole-stack split launch produces every gradient of the
+        # arena and nothing has to happen between gradient and update (no data-parallel all-reduce, no gradient scaling).
+        lin_ids = {id(q) for lin in self.linears for q in (lin.weight, lin.bias)}
+        adam = bool(self.split_wgrad and self.fused_backward and self.grouped_wgrad and self.buckets is None
+                    and self.world * self.dry_ranks == 1 and all(lin.bias is not None for lin in self.linears)
+                    and all(id(q) in lin_ids for q in self.f.parameters()))
+        tail = bool(adam and self.chain_tail and self.dz_out[0] is not None and
+                    ops.mlp_chain_tail_supported([tuple(lin.weight.shape) for lin in self.linears]))
+        # the chain runs with its tail directly on dy: no pool beyond this rank's rows, no output head -- then it can finish dy itself
+        on_dy = tail and not self.dp and self.emulate_pool <= 1 and self.head is None
+        dy_parts, mse = self._objective_folds(on_dy)
+        return StepPlan(adam_in_wgrad=adam, chain_tail=tail, dy_from_partials=bool(dy_parts), mse_in_chain=bool(mse),
+                        guard_rides=self._guard_rides, wgrad_halves=self.wgrad_halves)
 
     # -------------------------------------------------------------------------------- arenas
     def _flatten_parameters(self):
@@ -233,10 +302,6 @@ class ContrastiveTrainer:
                 self._layer_slices[0] = (min(lo, o), max(hi, o + (k + 3) // 4 * 4))
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
 
-    def _enc_rows(self) -> int:
-        """Rows the encoder runs on per step: the pair z, z~ stacked."""
-        return 2 * self.B
-
     def _allocate(self):
         dev, B, n = self.device, self.B, self.n
         R = self._enc_rows()
@@ -273,7 +338,7 @@ class ContrastiveTrainer:
         self.acts_out = list(self.acts)                      # what the forward writes as fp32 (None: planes only)
         self.dz_out = list(self.dz) if self.dz is not None else None
         if self.split_wgrad:
-            keep = bool(getattr(self, "keep_fp32_copies", False))          # (inspection: also write every fp32 copy)
+            keep = bool(self.keep_fp32_copies)
             for l in range(L):
                 if kinds[l] == 0:                            # dW_l = dZ_l^T acts_{l-1} on the bf16 / fp16 matrix cores
                     self.act_planes[l - 1] = ops.mlp_planes_alloc(R, widths[l - 1], True, dev, f16=self.split_f16)
@@ -289,12 +354,12 @@ class ContrastiveTrainer:
         # that an HBM-bound conversion kernel makes of the fp32 activations / gradients (clica_mlp_planes_from_f32)
         self.split_wgrad_wide = bool(self._want_split and not self.fused_forward and not self.fused_backward
                                      and all(lin.bias is not None for lin in self.linears))
+        self.wide_kinds = [ops.mlp_wgrad_split_kind(lin.out_features, lin.in_features) for lin in self.linears] if self.split_wgrad_wide else []
+        in_w = [lin.in_features for lin in self.linears]
         if self.split_wgrad_wide:
             # (round 5) the per-layer split kernels in the f16x2 arithmetic too: plane copies of 4 B/element, three products, per-tensor scales
             # in the same Split16 state (tensor = (family, layer): activations by the layer they feed, gradients and weights by their layer)
             self.split_f16_wide = f16w = bool(self._arith_f16 and L <= 8)
-            self.wide_kinds = [ops.mlp_wgrad_split_kind(lin.out_features, lin.in_features) for lin in self.linears]
-            in_w = [lin.in_features for lin in self.linears]
             self.xin_planes = [ops.mlp_planes_alloc(R, in_w[l], True, dev, f16=f16w) if self.wide_kinds[l] == 0 else None for l in range(L)]
             self.dzw_planes = [ops.mlp_planes_alloc(R, widths[l], False, dev, f16=f16w) if self.wide_kinds[l] == 0 else None for l in range(L)]
             shapes = [tuple(lin.weight.shape) for lin in self.linears]
@@ -307,14 +372,11 @@ class ContrastiveTrainer:
         # T-planes for the next chain layer, N-planes for the next layer's weight gradient, fp32 only where an fp32 kernel follows.
         self.chain = set()
         if self.split_wgrad_wide:
-            in_w = [lin.in_features for lin in self.linears]
             # (bf16x3: 1024 -- with the 400-wide layers in the chain one p = 1 gradient check of G13 measures 1.1e-5; f16x2: 384 -- all of
             #  config 3's checks hold 1e-5 and the step gains 13 %: 198 -> 225 steps/s)
             cmin = 384 if self.split_f16_wide else 1024
             self.chain = {l for l in range(1, L - 1) if self.wide_kinds[l] == 0 and in_w[l] >= cmin and widths[l] >= cmin}
-        if self.chain:
-            in_w = [lin.in_features for lin in self.linears]
-            f16w = self.split_f16_wide
+        if self.chain:                      # (only under split_wgrad_wide: f16w is set)
             self.wT = {l: ops.mlp_planes_alloc(in_w[l], widths[l], False, dev, f16=f16w) for l in self.chain}      # planes of W^T
             self.wN = {l: ops.mlp_planes_alloc(widths[l], in_w[l], False, dev, f16=f16w) for l in self.chain}      # planes of W
             self.xT = {l: ops.mlp_planes_alloc(in_w[l], R, False, dev, f16=f16w) for l in self.chain}              # T-planes of the layer input
@@ -324,50 +386,14 @@ class ContrastiveTrainer:
             self._wide_packed = False
         if self.head is not None:
             self.head_part = torch.empty(((R + 255) // 256, n if isinstance(self.head, ls.SoftclipLayer) else 1), **f32)
-            hp = self.head.r if isinstance(self.head, ls.RescaleLayer) else self.head.max_abs_bound
+            self._head_src = hp = self.head.r if isinstance(self.head, ls.RescaleLayer) else self.head.max_abs_bound
             self.head_param = hp.data if isinstance(hp, nn.Parameter) else hp.to(dev).contiguous()
             self.head_learnable = isinstance(hp, nn.Parameter)
             self.dpre = torch.empty((R, n), **f32)
 
-    def _allocate_loss(self, R):
-        """Buffers of the objective: the InfoNCE loss of the pair -- Lp distances for p >= 1, dot products for p = 0 (the dot kind's
-        training pair) -- with its outputs, its workspace and the negatives pool under data parallelism."""
-        dev, B, n = self.device, self.B, self.n
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.dy = torch.empty((R, n), **f32)
-        self.loss_out = torch.empty(3 * B + 3, **f32)
-        Bg = B * self.world * self.emulate_pool * self.dry_ranks
-        pooled = self.dp or self.emulate_pool > 1
-        self.z_all = torch.empty((Bg, n), **f32) if pooled else None
-        self.lse_all = torch.empty((Bg,), **f32) if pooled else None
-        if self.dot:
-            # dot-product InfoNCE: one training pair (forward with its tile finisher, symmetric backward + reduction); its workspace
-            # holds arrival counters that must start at zero
-            self.desc = _lib.DotLossDesc(B=B, B3=Bg, n=n, tau=self.tau, alpha=self.alpha, normalize=0)
-            tb = C.c_size_t()
-            _lib.check(_lib.load().clica_dot_loss_train_workspace_bytes(C.byref(self.desc), C.byref(tb)), "dot train workspace")
-            self.loss_ws = torch.zeros(tb.value, dtype=torch.uint8, device=dev)
-            self.loss_train = True
-            self.early_tick = True
-            self._ticked = False
-            return
-        self.desc = _lib.LpLossDesc(B=B, B3=Bg, n=n, p=self.p, tau=self.tau, alpha=self.alpha, compat=1, pow=1)
-        fb, bb = C.c_size_t(), C.c_size_t()
-        _lib.check(_lib.load().clica_lp_loss_workspace_bytes(C.byref(self.desc), C.byref(fb), C.byref(bb)), "workspace")
-        tb = C.c_size_t()
-        self.loss_train = self.p >= 1                  # fused training pair of loss entry points
-        if self.loss_train:
-            _lib.check(_lib.load().clica_lp_loss_train_workspace_bytes(C.byref(self.desc), C.byref(tb)), "train workspace")
-        self.loss_ws = torch.zeros(max(fb.value, bb.value, tb.value), dtype=torch.uint8, device=dev)
-        # the step / RNG counter is advanced by the loss backward's reduction launch (all samplers of the step have run by then)
-        # instead of a separate one-thread launch at the end; Adam then takes t = counter
-        self.early_tick = self.loss_train
-        self._ticked = False
-
-
     def _init_wide_ones(self):
         """The fused epilogues of the wide chain never touch the constant-1 column of the N-planes they fill: written once here."""
-        if not getattr(self, "chain", None):
+        if not self.chain:
             return
         L, R = len(self.linears), self._enc_rows()
         widths = [lin.out_features for lin in self.linears]
@@ -386,21 +412,9 @@ class ContrastiveTrainer:
         s, B, n = self.sampler, self.B, self.n
         z, zt = self.z[:B], self.z[B:]
         sid = 2 * self.rank
-        mean = None
-        if s.marginal != "uniform":
-            if not hasattr(self, "_eta"):
-                self._eta = torch.zeros(1, n, device=self.device)
-                if s.space == "sphere":
-                    self._eta[0, 0] = 1.0                      # main_mlp.py:148-150
-            mean = self._eta
         # both draws in one launch for the coordinate-wise kinds (box, R^n); two for the sphere / vMF
-        ops.sample_pair(s.space, s.marginal, s.conditional, n, B, z, zt, marginal_mean=mean, m_scale=s.m_param, m_p=s.m_p,
+        ops.sample_pair(s.space, s.marginal, s.conditional, n, B, z, zt, marginal_mean=self._eta, m_scale=s.m_param, m_p=s.m_p,
                         c_scale=s.c_param, c_p=s.c_p, box=s.box, seed=s.seed, stream_id=sid, step_dev=self.step_dev)
-        self._mix()
-
-    def inject(self, z1: torch.Tensor, z2: torch.Tensor):
-        """Use caller-provided latents instead of the device sampler (parity tests)."""
-        self.z[:self.B].copy_(z1); self.z[self.B:].copy_(z2)
         self._mix()
 
     def _mix(self):
@@ -416,15 +430,8 @@ class ContrastiveTrainer:
         if self.s16 is None or not self.split_bf16 or self.packed is None or self.packed_t is None:
             return False
         s, B, n = self.sampler, self.B, self.n
-        mean = None
-        if s.marginal != "uniform":
-            if not hasattr(self, "_eta"):
-                self._eta = torch.zeros(1, n, device=self.device)
-                if s.space == "sphere":
-                    self._eta[0, 0] = 1.0                      # main_mlp.py:148-150
-            mean = self._eta
         ops.mlp_pack_split16_sample([lin.weight for lin in self.linears], self.packed, self.packed_t, self.s16, s.space, s.marginal,
-                                    s.conditional, n, B, self.z[:B], self.z[B:], marginal_mean=mean, m_scale=s.m_param, m_p=s.m_p,
+                                    s.conditional, n, B, self.z[:B], self.z[B:], marginal_mean=self._eta, m_scale=s.m_param, m_p=s.m_p,
                                     c_scale=s.c_param, c_p=s.c_p, box=s.box, seed=s.seed, stream_id=2 * self.rank, step_dev=self.step_dev)
         self._packed_current = True
         self._mix()
@@ -462,8 +469,7 @@ class ContrastiveTrainer:
                             signmasks=self.signmasks, mix=mix)
             cur = self.acts[-1]
         else:
-            wide = getattr(self, "split_wgrad_wide", False)
-            chain = getattr(self, "chain", set())
+            wide, chain = self.split_wgrad_wide, self.chain
             if chain and not (self._wide_packed and self._packed_current):
                 for l in chain:                             # plane copies of the CURRENT weights, both orientations
                     ops.mlp_planes_from_f32_t(self.linears[l].weight, out=self.wT[l], **self._s16w(2, l))
@@ -497,125 +503,6 @@ class ContrastiveTrainer:
                 _lib.check(lib.clica_softclip_fwd(cur.data_ptr(), n, self.head_param.data_ptr(), self.y.data_ptr(), n, R, n, st),
                            "clica_softclip_fwd")
 
-    def loss_forward_backward(self):
-        """Loss forward + its backward w.r.t. the embeddings.  The negatives are "all z1_rec of the (global)
-        batch" (the reference's roll, main_mlp.py:272, up to a permutation), so the pair matrix is symmetric
-        and ONE backward sweep with both rows' softmax statistics gives dz1 complete: no row pass, no column
-        pass, and under data parallelism no reduce-scatter of d/dz3 -- only an all-gather of the B
-        log-sum-exp values next to the all-gather of the embeddings."""
-        lib, st = _lib.load(), _lib.stream_ptr()
-        B, n, o = self.B, self.n, self.loss_out
-        y1, y2 = self.y[:B], self.y[B:]
-        lse = o[2 * B:3 * B]
-        emu = self.emulate_pool > 1
-        dry = self.dry_ranks > 1
-        if self.dp:
-            dist.all_gather_into_tensor(self.z_all[:B * self.world] if dry else self.z_all, y1.contiguous(), group=self.pg)
-            if dry:      # the other ranks' rows: copies of this rank's
-                self.z_all.view(self.dry_ranks, B, n)[1:].copy_(self.z_all[:B].unsqueeze(0))
-            pool = self.z_all
-        elif emu:
-            self.z_all.view(self.emulate_pool, B, n).copy_(y1.unsqueeze(0))
-            pool = self.z_all
-        else:
-            pool = y1
-        if self.dot:
-            self._dot_forward_backward(y1, y2, pool, lse, emu, dry)
-            return
-        if self.loss_train:
-            # forward + coefficient step (finalize), then -- after the all-gather of the row statistics under DP -- pair sweep +
-            # reduction (+ the forward's means): 5 launches instead of 8
-            _lib.check(lib.clica_lp_loss_fwd_train(C.byref(self.desc), y1.data_ptr(), n, y2.data_ptr(), n, pool.data_ptr(), n,
-                                                   o[:B].data_ptr(), o[B:2 * B].data_ptr(), lse.data_ptr(),
-                                                   self.dy[:B].data_ptr(), n, self.dy[B:].data_ptr(), n,
-                                                   self.loss_ws.data_ptr(), self.loss_ws.numel(), st), "clica_lp_loss_fwd_train")
-            if self.dp:
-                dist.all_gather_into_tensor(self.lse_all[:B * self.world] if dry else self.lse_all, lse, group=self.pg)
-                if dry:
-                    self.lse_all.view(self.dry_ranks, B)[1:].copy_(self.lse_all[:B].unsqueeze(0))
-            elif emu:
-                self.lse_all.view(self.emulate_pool, B).copy_(lse.unsqueeze(0))
-            pool_lse = self.lse_all if (self.dp or emu) else lse
-            self._dy_parts = None
-            if self._chain_takes_partials(emu):
-                # N = 1 training step: no reduction launch -- the backward chain's prologue sums the pair sweep's partials into dy, leaves
-                # the forward's means and ticks the counter (clica_lp_dy_parts; same sums in the same order)
-                self._dy_parts = _lib.DyParts()
-                self._dy_parts_taken = getattr(self, "_dy_parts_taken", 0) + 1      # (tests: which path a trainer took)
-                _lib.check(lib.clica_lp_loss_bwd_sym_train_parts(C.byref(self.desc), y1.data_ptr(), n, pool.data_ptr(), n,
-                                                                 lse.data_ptr(), pool_lse.data_ptr(), o[3 * B:].data_ptr(),
-                                                                 self.step_dev.data_ptr() if self.early_tick else None,
-                                                                 self.loss_ws.data_ptr(), self.loss_ws.numel(), C.byref(self._dy_parts), st),
-                           "clica_lp_loss_bwd_sym_train_parts")
-                self._ticked = self.early_tick
-                return
-            _lib.check(lib.clica_lp_loss_bwd_sym_train(C.byref(self.desc), y1.data_ptr(), n, pool.data_ptr(), n,
-                                                       lse.data_ptr(), pool_lse.data_ptr(), self.dy[:B].data_ptr(), n, o[3 * B:].data_ptr(),
-                                                       self.step_dev.data_ptr() if self.early_tick else None,
-                                                       self.loss_ws.data_ptr(), self.loss_ws.numel(), st), "clica_lp_loss_bwd_sym_train")
-            self._ticked = self.early_tick
-            return
-        _lib.check(lib.clica_lp_loss_fwd(C.byref(self.desc), y1.data_ptr(), n, y2.data_ptr(), n, pool.data_ptr(), n,
-                                         o[:B].data_ptr(), o[B:2 * B].data_ptr(), lse.data_ptr(), o[3 * B:].data_ptr(),
-                                         None, 0, self.loss_ws.data_ptr(), self.loss_ws.numel(), st), "clica_lp_loss_fwd")
-        if self.dp:
-            dist.all_gather_into_tensor(self.lse_all[:B * self.world] if dry else self.lse_all, lse, group=self.pg)
-            if dry:
-                self.lse_all.view(self.dry_ranks, B)[1:].copy_(self.lse_all[:B].unsqueeze(0))
-            pool_lse = self.lse_all
-        elif emu:
-            self.lse_all.view(self.emulate_pool, B).copy_(lse.unsqueeze(0))
-            pool_lse = self.lse_all
-        else:
-            pool_lse = lse
-        _lib.check(lib.clica_lp_loss_bwd_sym(C.byref(self.desc), y1.data_ptr(), n, y2.data_ptr(), n, pool.data_ptr(), n,
-                                             lse.data_ptr(), pool_lse.data_ptr(), None, None, None,
-                                             self.dy[:B].data_ptr(), n, self.dy[B:].data_ptr(), n,
-                                             self.loss_ws.data_ptr(), self.loss_ws.numel(), st), "clica_lp_loss_bwd_sym")
-
-    def _dot_forward_backward(self, y1, y2, pool, lse, emu, dry):
-        """p = 0: the dot kind's training pair.  Forward (one launch: pair sweep + tile finisher; writes loss_i, pos_i, lse_i and the
-        positive-pair part of dy), the all-gather of the row log-sum-exps under data parallelism, then the symmetric sweep and the
-        reduction launch that adds it into dy[:B], writes the three means and advances the step counter."""
-        lib, st = _lib.load(), _lib.stream_ptr()
-        B, n, o = self.B, self.n, self.loss_out
-        _lib.check(lib.clica_dot_loss_fwd_train(C.byref(self.desc), y1.data_ptr(), n, y2.data_ptr(), n, pool.data_ptr(), n,
-                                                o[:B].data_ptr(), o[B:2 * B].data_ptr(), lse.data_ptr(),
-                                                self.dy[:B].data_ptr(), n, self.dy[B:].data_ptr(), n,
-                                                self.loss_ws.data_ptr(), self.loss_ws.numel(), st), "clica_dot_loss_fwd_train")
-        if self.dp:
-            dist.all_gather_into_tensor(self.lse_all[:B * self.world] if dry else self.lse_all, lse, group=self.pg)
-            if dry:
-                self.lse_all.view(self.dry_ranks, B)[1:].copy_(self.lse_all[:B].unsqueeze(0))
-        elif emu:
-            self.lse_all.view(self.emulate_pool, B).copy_(lse.unsqueeze(0))
-        pool_lse = self.lse_all if (self.dp or emu) else lse
-        self._dy_parts = None
-        _lib.check(lib.clica_dot_loss_bwd_sym_train(C.byref(self.desc), y1.data_ptr(), n, pool.data_ptr(), n,
-                                                    lse.data_ptr(), pool_lse.data_ptr(), self.dy[:B].data_ptr(), n, o[3 * B:].data_ptr(),
-                                                    self.step_dev.data_ptr() if self.early_tick else None,
-                                                    self.loss_ws.data_ptr(), self.loss_ws.numel(), st), "clica_dot_loss_bwd_sym_train")
-        self._ticked = self.early_tick
-
-    # Test hooks (class attributes, tests/test_gpu_engine.py): both the folded and the unfolded launch structures are product paths -- the
-    # unfolded ones run under data parallelism and behind a head -- and the equivalence tests compare them on ONE trainer configuration.
-    chain_tail = True            # the backward chain's tail writes the n-wide layers' weight-gradient slabs (clica_mlp_dgrad_split_tail)
-    fold_dy_reduce = True        # ... and its prologue finishes dy from the loss sweep's partials (no reduction launch)
-
-    def _chain_tail_ok(self) -> bool:
-        if not hasattr(self, "_tail_ok"):
-            self._tail_ok = (self.chain_tail and self.dz_out[0] is not None and
-                             ops.mlp_chain_tail_supported([tuple(lin.weight.shape) for lin in self.linears]))
-        return self._tail_ok
-
-    def _chain_takes_partials(self, emu: bool) -> bool:
-        """Will THIS step's backward chain run with its tail (clica_mlp_dgrad_split_tail) directly on dy?  Then it can finish dy itself."""
-        if not self.fold_dy_reduce or not getattr(self, "_in_step", False):
-            return False
-        if self.dp or emu or self.head is not None or not (self.split_bf16 and self.split_wgrad and self.fused_backward):
-            return False
-        return self._adam_folds_into_wgrad() and self._chain_tail_ok()
-
     def _head_backward(self):
         """d loss / d (pre-head output): the head's backward (and its parameter gradient), or dy itself."""
         lib, st = _lib.load(), _lib.stream_ptr()
@@ -631,8 +518,7 @@ class ContrastiveTrainer:
                 _lib.check(lib.clica_softclip_bwd(pre.data_ptr(), n, self.head_param.data_ptr(), g.data_ptr(), n,
                                                   self.dpre.data_ptr(), n, _lib.ptr(part), R, n, st), "clica_softclip_bwd")
             if self.head_learnable:
-                hp = self.head.r if isinstance(self.head, ls.RescaleLayer) else self.head.max_abs_bound
-                torch.sum(self.head_part, dim=0, out=self._gviews[id(hp)])
+                torch.sum(self.head_part, dim=0, out=self._gviews[id(self._head_src)])
             g = self.dpre
         return g
 
@@ -645,20 +531,19 @@ class ContrastiveTrainer:
         if not self._packed_current:
             self.pack()
         if self.split_bf16:
-            tail = None
-            self._tail_ready = False
-            if getattr(self, "_fold_adam", False) and self.split_wgrad:
+            h, tail = self.handoff, None
+            h.tail_ready = False
+            if h.fold_adam and self.plan.chain_tail:
                 # inside a training step (N = 1): the chain's workgroups also leave the n-wide first / last layer's weight-gradient
                 # slabs (clica_mlp_dgrad_split_tail) -- weight_grads() then needs no tiny-dimension launch
-                if self._chain_tail_ok():
-                    tail = dict(a_last=self.acts_out[L - 2], x=self.x, shapes=[tuple(lin.weight.shape) for lin in self.linears], ws=self.group_ws,
-                                dy_parts=getattr(self, "_dy_parts", None), mse=getattr(self, "_mse_fold", None))
-                    self._tail_ready = True
-            if getattr(self, "_dy_parts", None) is not None and (tail is None or g is not self.dy):
+                tail = dict(a_last=self.acts_out[L - 2], x=self.x, shapes=[tuple(lin.weight.shape) for lin in self.linears], ws=self.group_ws,
+                            dy_parts=h.dy_parts, mse=h.mse)
+                h.tail_ready = True
+            if h.dy_parts is not None and (tail is None or g is not self.dy):
                 raise _lib.ClicaError("engine: the loss left its partials for the backward chain, but the chain does not run with its tail on dy")
-            if getattr(self, "_mse_fold", None) is not None and (tail is None or g is not self.dy):
+            if h.mse is not None and (tail is None or g is not self.dy):
                 raise _lib.ClicaError("engine: the MSE objective was left to the backward chain, but the chain does not run with its tail on dy")
-            self._dy_parts = self._mse_fold = None
+            h.dy_parts = h.mse = None
             ops.mlp_dgrad_chain_split(g, ws, self.packed_t, [self.dz_out[l - 1] for l in chain], self.slope,
                                       masks_chain=[self.signmasks[l - 1] for l in chain],
                                       planes=[self.dz_planes[l - 1] for l in chain] if self.split_wgrad else None, state=self.s16, tail=tail)
@@ -675,21 +560,21 @@ class ContrastiveTrainer:
         dWs = [self._gviews[id(self.linears[l].weight)] for l in order]
         dbs = [self._gviews[id(self.linears[l].bias)] for l in order]
         if self.split_wgrad:
-            adam = None
-            if getattr(self, "_fold_adam", False) and layers is None:
+            h, adam = self.handoff, None
+            if h.fold_adam and layers is None:
                 # inside a training step (N = 1): the reduction launch that ends the weight gradients applies the optimizer as well
                 # (clica_mlp_wgrad_split_adam) -- optimizer_step() then has nothing left to launch
                 adam = dict(param=self.param_arena, grad=self.grad_arena, exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq,
                             step_dev=self.step_dev, lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
-                            grad_scale=1.0, t_offset=0 if self._ticked else 1, s16=self.s16)
+                            grad_scale=1.0, t_offset=0 if h.ticked else 1, s16=self.s16)
             ops.mlp_wgrad_split(R, [self.dz_planes[l] for l in order], [self.act_planes[l - 1] if l > 0 else None for l in order],
                                 [g if l == L - 1 else self.dz_out[l] for l in order],
                                 [self.acts_out[l - 1] if l > 0 else self.x for l in order], dWs, dbs, ws=self.group_ws,
                                 state=self.s16, a_index=order, d_index=[L - 1 - l for l in order], adam=adam,
-                                tail_slabs=adam is not None and getattr(self, "_tail_ready", False))
-            self._tail_ready = False
+                                tail_slabs=adam is not None and h.tail_ready)
+            h.tail_ready = False
             if adam is not None:
-                self._adam_done = True
+                h.adam_done = True
         else:
             ops.mlp_wgrad([g if l == L - 1 else self.dz[l] for l in order],
                           [self.acts[l - 1] if l > 0 else self.x for l in order], dWs, dbs, ws=self.group_ws)
@@ -701,8 +586,8 @@ class ContrastiveTrainer:
         R, w = self.x.shape[0], self.linears[l].out_features
         # f16x2: the planes are scaled by the activation scale the pass that WROTE them ran with -- the scales in force if no update has run
         # since (a bare forward(), a calibration pass), the previous ones (kept by the update) after a full step
-        which = "scales_a" if getattr(self, "_planes_on_current_scales", False) else "last_scales_a"
-        if l in getattr(self, "chain", set()) and (l + 1) in self.chain:
+        which = "scales_a" if self._planes_on_current_scales else "last_scales_a"
+        if l in self.chain and (l + 1) in self.chain:
             if self.split_f16_wide:
                 return ops.mlp_planes16_to_f32(self.xin_planes[l + 1], R, w, True, self.s16.read()[which][l + 1])
             return ops.mlp_planes_to_f32(self.xin_planes[l + 1], R, w, True)
@@ -717,7 +602,7 @@ class ContrastiveTrainer:
         kernel on plane copies (dZ converted here, the layer input converted in forward())."""
         lin = self.linears[l]
         dW, db = self._gviews[id(lin.weight)], self._gviews[id(lin.bias)]
-        if getattr(self, "split_wgrad_wide", False) and self.wide_kinds[l] == 0:
+        if self.split_wgrad_wide and self.wide_kinds[l] == 0:
             if not planes_ready:                            # (a split data-gradient epilogue has written dZ_l's planes already)
                 ops.mlp_planes_from_f32(g, False, out=self.dzw_planes[l], **self._s16w(1, l))
             ops.mlp_wgrad_split(self.x.shape[0], [self.dzw_planes[l]], [self.xin_planes[l]], [None], [None], [dW], [db], ws=self.wide_ws,
@@ -733,7 +618,7 @@ class ContrastiveTrainer:
         two = side is not None and main is not None
         if self.fused_backward:
             # (1) the data-gradient chain in one launch; (2) the weight-gradient GEMMs
-            st = getattr(self, "stamps", None)
+            st = self.stamps
             if st:
                 ops.stamp(st["mlp_dgrad"], 0)
             self.backward_chain(g)
@@ -789,7 +674,7 @@ class ContrastiveTrainer:
         reader_done = {}        # dZ buffer index -> event of the wgrad that reads it
         buf_of_g = None         # index into self.dbuf holding the current dZ (None: self.dy / self.dpre, or planes only)
         nxt = 0
-        chain = getattr(self, "chain", set())
+        chain = self.chain
         R = self.x.shape[0]
         dzN_ready = dzT_ready = False       # dZ_l already sits in dzw_planes[l] / dzT[l] (written by a split data-gradient epilogue)
         for l in reversed(range(L)):
@@ -847,29 +732,21 @@ class ContrastiveTrainer:
             dist.all_reduce(self._guard_slot, op=dist.ReduceOp.SUM, group=self.pg)
 
     def _adam_folds_into_wgrad(self) -> bool:
-        """The optimizer can ride in the weight-gradient reduction when ONE whole-stack split launch produces every gradient of the
-        arena and nothing has to happen between gradient and update (no data-parallel all-reduce, no gradient scaling)."""
-        if not (self.split_wgrad and self.fused_backward and self.grouped_wgrad) or self.buckets is not None:
-            return False
-        if self.world * self.dry_ranks != 1:
-            return False
-        lin_ids = {id(q) for lin in self.linears for q in (lin.weight, lin.bias)}
-        return all(lin.bias is not None for lin in self.linears) and all(id(q) in lin_ids for q in self.f.parameters())
+        """Does the weight-gradient reduction of a step apply the optimizer as well (StepPlan.adam_in_wgrad)?"""
+        return self.plan.adam_in_wgrad
 
     def optimizer_step(self):
         self._packed_current = False
-        if getattr(self, "_adam_done", False):       # applied by the weight-gradient reduction of this step (weight_grads)
-            self._adam_done = False
-            ticked, self._ticked = self._ticked, False
-            self._s16_updated = self.s16 is not None
-            if not ticked:
-                ops.tick(self.step_dev)
-            return
-        ticked, self._ticked = self._ticked, False
-        fused_update = ops.adam_step(self.param_arena, self.grad_arena, self.exp_avg, self.exp_avg_sq, self.step_dev, self.lr,
-                                     self.betas[0], self.betas[1], self.eps, grad_scale=1.0 / (self.world * self.dry_ranks),
-                                     t_offset=0 if ticked else 1, s16=self.s16)
-        self._s16_updated = bool(fused_update)
+        h = self.handoff
+        ticked, h.ticked = h.ticked, False
+        if h.adam_done:       # applied by the weight-gradient reduction of this step (weight_grads)
+            h.adam_done = False
+            h.scales_updated = self.s16 is not None
+        else:
+            fused_update = ops.adam_step(self.param_arena, self.grad_arena, self.exp_avg, self.exp_avg_sq, self.step_dev, self.lr,
+                                         self.betas[0], self.betas[1], self.eps, grad_scale=1.0 / (self.world * self.dry_ranks),
+                                         t_offset=0 if ticked else 1, s16=self.s16)
+            h.scales_updated = bool(fused_update)
         if not ticked:
             ops.tick(self.step_dev)
 
@@ -887,22 +764,23 @@ class ContrastiveTrainer:
                 self.sample()
             if fused:
                 self.pack()                    # (here, not inside forward(): bench.py's stamps bracket the encoder launch alone)
-        st = getattr(self, "stamps", None)         # bench.py: device time stamps around the encoder launches, valid inside the graph
+        st = self.stamps
         if st:
             ops.stamp(st["null"], 0); ops.stamp(st["null"], 1)      # empty bracket: the stamp pair's own cost, subtracted by the reader
             ops.stamp(st["mlp_fwd"], 0)
         self.forward()
         if st:
             ops.stamp(st["mlp_fwd"], 1)
-        self._in_step = True                   # (loss_forward_backward may leave dy to be finished by this step's backward chain)
+        h = self.handoff
+        h.in_step = True                       # (loss_forward_backward may leave dy to be finished by this step's backward chain)
         try:
             self.loss_forward_backward()
-            self._fold_adam = self._adam_folds_into_wgrad()
+            h.fold_adam = self.plan.adam_in_wgrad
             self.backward()
         finally:
-            self._fold_adam = self._in_step = False
+            h.reset("fold_adam", "in_step")
         self.optimizer_step()
-        if self.s16 is not None and not getattr(self, "_s16_updated", False):
+        if self.s16 is not None and not h.scales_updated:
             self.s16.update()                  # this step's recorded maxima -> the next step's scales (normally inside the Adam launch)
         self._planes_on_current_scales = False     # (an update has run behind the forward that wrote the planes)
 
@@ -932,7 +810,7 @@ class ContrastiveTrainer:
             self.s16.update()
             self._planes_on_current_scales = False
             self.step_dev.copy_(tick)
-            self._ticked = False
+            self.handoff.reset("ticked")
         self.s16.clear_flags()                   # the first pass ran on scales of 1: whatever it flagged is not a finding
         self._versions_seen = self._param_versions()
         self._guard_skipped_seen = self.s16.guard()["skipped"]      # (calibration passes the guard withheld are not training steps)
@@ -981,13 +859,12 @@ class ContrastiveTrainer:
         """The `arith` string of arith_state() (no device read)."""
         if self.s16 is not None:
             return "f16x2" if self.split_f16 else "f16x2 (per-layer wide path; narrow layers native fp32 MFMA)"
-        if not (self.split_bf16 or getattr(self, "split_wgrad_wide", False)):
+        if not (self.split_bf16 or self.split_wgrad_wide):
             return "native_fp32"
         return "bf16x3"
 
     # -------------------------------------------------------------------------------- checkpoints
     STATE_FORMAT, STATE_VERSION = "cl_ica_amd.trainer", 1
-    _kind = "contrastive"
 
     def _head_name(self) -> str:
         if self.head is None:
@@ -1002,6 +879,13 @@ class ContrastiveTrainer:
         return dict(sampler=samp, batch_size=self.B, p=self.p, tau=self.tau, alpha=self.alpha, g_weights=self.gW.detach().cpu().clone(),
                     g_slope=self.g_slope, g_act_kind=self.g_act_kind, world=self.world, dry_ranks=self.dry_ranks,
                     layer_shapes=[[int(lin.out_features), int(lin.in_features)] for lin in self.linears], head=self._head_name())
+
+    def _loss_state(self):
+        """What the objective's workspace carries from step to step, as the library's opaque blob (None: nothing)."""
+        return None
+
+    def _load_loss_state(self, blob):
+        pass
 
     def _not_in_capture(self, what: str):
         if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
@@ -1018,7 +902,7 @@ class ContrastiveTrainer:
         self._not_in_capture("state_dict()")
         cuda = self.device.type == "cuda"
         s16_blob = self.s16.export_state() if self.s16 is not None else None
-        loss_blob = ops.lp_loss_train_state_export(self.desc, self.loss_ws) if (cuda and self.loss_train and not self.dot) else None
+        loss_blob = self._loss_state() if cuda else None
         f_sd = self.f.state_dict()
         dev = [self.exp_avg, self.exp_avg_sq, self.step_dev] + list(f_sd.values()) + [b for b in (s16_blob, loss_blob) if b is not None]
         if cuda:        # every read queued behind the step's launches, one wait for all of them
@@ -1114,16 +998,15 @@ class ContrastiveTrainer:
                 self.s16.import_state(arith["split16"])
                 self._s16_calibrated = bool(arith["s16_calibrated"])
                 self._guard_skipped_seen = self.s16.guard()["skipped"]
-            if arith["loss"] is not None and cuda and self.loss_train and not self.dot:
-                ops.lp_loss_train_state_import(self.desc, self.loss_ws, arith["loss"])
+            if arith["loss"] is not None and cuda:
+                self._load_loss_state(arith["loss"])
         else:
             self._s16_calibrated = False
         # the load is not an "external write": what the kernels derive from the parameters is marked stale, nothing is re-measured
         self._versions_seen = self._param_versions()
         self._packed_current = False
         self._x_pending = False
-        self._ticked = self._adam_done = False
-        self._dy_parts = self._mse_fold = None
+        self.handoff.reset()
         ops.PARAM_EPOCH += 1
         if not exact and self.s16 is not None and self.graph is not None:
             self.calibrate_scales(True)        # a replayed graph cannot calibrate on its own (as _check_external_writes does)
@@ -1143,15 +1026,12 @@ class ContrastiveTrainer:
             self._step_body(True)
         return self._result()
 
-    def step_injected(self, z1, z2):
+    def step_injected(self, z1, z2=None):
         self._check_external_writes()
         self.inject(z1, z2)
         self._step_body(False)
         ops.PARAM_EPOCH += 1
         return self._result()
-
-    def _result(self) -> torch.Tensor:
-        return self.loss_out[3 * self.B:]
 
     def capture(self, warmup: int = 3):
         """Capture the step into a HIP graph (counters and RNG offsets live on device, so replays
@@ -1203,6 +1083,160 @@ class ContrastiveTrainer:
         self.graph = graph
         return graph
 
+    @property
+    def steps_done(self) -> int:
+        return int(self.step_dev.item())
+
+
+class ContrastiveTrainer(_FusedTrainer):
+    """The fused step with the pair's InfoNCE objective (the module's docstring); keywords beyond `device` are _FusedTrainer's."""
+    fold_dy_reduce = True        # test hook, as chain_tail: the chain's prologue finishes dy from the loss sweep's partials (no reduction launch)
+    _kind = "contrastive"
+
+    def __init__(self, f: nn.Sequential, g_weights: torch.Tensor, sampler: SamplerSpec, batch_size: int,
+                 p: float = 2, tau: float = 1.0, alpha: float = 0.5, lr: float = 1e-4, g_slope: float = 0.2,
+                 betas=(0.9, 0.999), eps: float = 1e-8, device=None, **engine):
+        self.p, self.tau, self.alpha = float(p), float(tau), float(alpha)
+        # p = 0: SimCLRLoss(normalize=False, tau, alpha) -- InfoNCE on dot products (losses.py:162-202), the objective of the
+        # reference's hypersphere experiment; the loss runs on the dot kind's training pair (csrc/dot_train.hip)
+        self.dot = self.p == 0
+        super().__init__(f, g_weights, sampler, batch_size, lr=lr, g_slope=g_slope, betas=betas, eps=eps, device=device, **engine)
+
+    def _enc_rows(self) -> int:
+        """Rows the encoder runs on per step: the pair z, z~ stacked."""
+        return 2 * self.B
+
+    def _allocate_loss(self, R):
+        """Buffers of the objective: the InfoNCE loss of the pair -- Lp distances for p >= 1, dot products for p = 0 (the dot kind's
+        training pair) -- with its outputs, its workspace and the negatives pool under data parallelism."""
+        dev, B, n = self.device, self.B, self.n
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.dy = torch.empty((R, n), **f32)
+        self.loss_out = torch.empty(3 * B + 3, **f32)
+        Bg = B * self.world * self.emulate_pool * self.dry_ranks
+        pooled = self.dp or self.emulate_pool > 1
+        self.z_all = torch.empty((Bg, n), **f32) if pooled else None
+        self.lse_all = torch.empty((Bg,), **f32) if pooled else None
+        if self.dot:
+            # dot-product InfoNCE: one training pair (forward with its tile finisher, symmetric backward + reduction); its workspace
+            # holds arrival counters that must start at zero
+            self.desc = _lib.DotLossDesc(B=B, B3=Bg, n=n, tau=self.tau, alpha=self.alpha, normalize=0)
+            tb = C.c_size_t()
+            _lib.check(_lib.load().clica_dot_loss_train_workspace_bytes(C.byref(self.desc), C.byref(tb)), "dot train workspace")
+            self.loss_ws = torch.zeros(tb.value, dtype=torch.uint8, device=dev)
+            self.loss_train = self.early_tick = True
+            return
+        self.desc = _lib.LpLossDesc(B=B, B3=Bg, n=n, p=self.p, tau=self.tau, alpha=self.alpha, compat=1, pow=1)
+        fb, bb = C.c_size_t(), C.c_size_t()
+        _lib.check(_lib.load().clica_lp_loss_workspace_bytes(C.byref(self.desc), C.byref(fb), C.byref(bb)), "workspace")
+        tb = C.c_size_t()
+        self.loss_train = self.p >= 1                  # fused training pair of loss entry points
+        if self.loss_train:
+            _lib.check(_lib.load().clica_lp_loss_train_workspace_bytes(C.byref(self.desc), C.byref(tb)), "train workspace")
+        self.loss_ws = torch.zeros(max(fb.value, bb.value, tb.value), dtype=torch.uint8, device=dev)
+        # the step / RNG counter is advanced by the loss backward's reduction launch (all samplers of the step have run by then)
+        # instead of a separate one-thread launch at the end; Adam then takes t = counter
+        self.early_tick = self.loss_train
+
+    def _objective_folds(self, on_dy: bool):
+        return on_dy and self.fold_dy_reduce and self.loss_train and not self.dot, False
+
+    def inject(self, z1: torch.Tensor, z2: torch.Tensor):
+        """Use caller-provided latents instead of the device sampler (parity tests)."""
+        self.z[:self.B].copy_(z1); self.z[self.B:].copy_(z2)
+        self._mix()
+
+    def _result(self) -> torch.Tensor:
+        return self.loss_out[3 * self.B:]
+
+    def _pooled(self, rows: torch.Tensor, pool: Optional[torch.Tensor]) -> torch.Tensor:
+        """This rank's `rows` (B of them) as every rank's: all-gathered into `pool` under data parallelism -- in a dry run the other
+        ranks' rows are copies of this rank's --, replicated into it for the emulated pool, themselves otherwise."""
+        B = self.B
+        if self.dp:
+            dry = self.dry_ranks > 1
+            dist.all_gather_into_tensor(pool[:B * self.world] if dry else pool, rows.contiguous(), group=self.pg)
+            if dry:
+                pool.view(self.dry_ranks, *rows.shape)[1:].copy_(pool[:B].unsqueeze(0))
+        elif self.emulate_pool > 1:
+            pool.view(self.emulate_pool, *rows.shape).copy_(rows.unsqueeze(0))
+        else:
+            return rows
+        return pool
+
+    def loss_forward_backward(self):
+        """Loss forward + its backward w.r.t. the embeddings.  The negatives are "all z1_rec of the (global)
+        batch" (the reference's roll, main_mlp.py:272, up to a permutation), so the pair matrix is symmetric
+        and ONE backward sweep with both rows' softmax statistics gives dz1 complete: no row pass, no column
+        pass, and under data parallelism no reduce-scatter of d/dz3 -- only an all-gather of the B
+        log-sum-exp values next to the all-gather of the embeddings."""
+        lib, st = _lib.load(), _lib.stream_ptr()
+        B, n, o, h = self.B, self.n, self.loss_out, self.handoff
+        y1, y2 = self.y[:B], self.y[B:]
+        lse = o[2 * B:3 * B]
+        pool = self._pooled(y1, self.z_all)
+        tick = self.step_dev.data_ptr() if self.early_tick else None
+        if self.dot:
+            self._dot_forward_backward(y1, y2, pool, lse, tick)
+            return
+        if self.loss_train:
+            # forward + coefficient step (finalize), then -- after the all-gather of the row statistics under DP -- pair sweep +
+            # reduction (+ the forward's means): 5 launches instead of 8
+            _lib.check(lib.clica_lp_loss_fwd_train(C.byref(self.desc), y1.data_ptr(), n, y2.data_ptr(), n, pool.data_ptr(), n,
+                                                   o[:B].data_ptr(), o[B:2 * B].data_ptr(), lse.data_ptr(),
+                                                   self.dy[:B].data_ptr(), n, self.dy[B:].data_ptr(), n,
+                                                   self.loss_ws.data_ptr(), self.loss_ws.numel(), st), "clica_lp_loss_fwd_train")
+            pool_lse = self._pooled(lse, self.lse_all)
+            h.dy_parts = None
+            if h.in_step and self.plan.dy_from_partials:
+                # N = 1 training step: no reduction launch -- the backward chain's prologue sums the pair sweep's partials into dy, leaves
+                # the forward's means and ticks the counter (clica_lp_dy_parts; same sums in the same order)
+                h.dy_parts = _lib.DyParts()
+                self._dy_parts_taken += 1
+                _lib.check(lib.clica_lp_loss_bwd_sym_train_parts(C.byref(self.desc), y1.data_ptr(), n, pool.data_ptr(), n,
+                                                                 lse.data_ptr(), pool_lse.data_ptr(), o[3 * B:].data_ptr(), tick,
+                                                                 self.loss_ws.data_ptr(), self.loss_ws.numel(), C.byref(h.dy_parts), st),
+                           "clica_lp_loss_bwd_sym_train_parts")
+            else:
+                _lib.check(lib.clica_lp_loss_bwd_sym_train(C.byref(self.desc), y1.data_ptr(), n, pool.data_ptr(), n,
+                                                           lse.data_ptr(), pool_lse.data_ptr(), self.dy[:B].data_ptr(), n, o[3 * B:].data_ptr(),
+                                                           tick, self.loss_ws.data_ptr(), self.loss_ws.numel(), st), "clica_lp_loss_bwd_sym_train")
+            h.ticked = self.early_tick
+            return
+        _lib.check(lib.clica_lp_loss_fwd(C.byref(self.desc), y1.data_ptr(), n, y2.data_ptr(), n, pool.data_ptr(), n,
+                                         o[:B].data_ptr(), o[B:2 * B].data_ptr(), lse.data_ptr(), o[3 * B:].data_ptr(),
+                                         None, 0, self.loss_ws.data_ptr(), self.loss_ws.numel(), st), "clica_lp_loss_fwd")
+        pool_lse = self._pooled(lse, self.lse_all)
+        _lib.check(lib.clica_lp_loss_bwd_sym(C.byref(self.desc), y1.data_ptr(), n, y2.data_ptr(), n, pool.data_ptr(), n,
+                                             lse.data_ptr(), pool_lse.data_ptr(), None, None, None,
+                                             self.dy[:B].data_ptr(), n, self.dy[B:].data_ptr(), n,
+                                             self.loss_ws.data_ptr(), self.loss_ws.numel(), st), "clica_lp_loss_bwd_sym")
+
+    def _dot_forward_backward(self, y1, y2, pool, lse, tick):
+        """p = 0: the dot kind's training pair.  Forward (one launch: pair sweep + tile finisher; writes loss_i, pos_i, lse_i and the
+        positive-pair part of dy), the all-gather of the row log-sum-exps under data parallelism, then the symmetric sweep and the
+        reduction launch that adds it into dy[:B], writes the three means and advances the step counter."""
+        lib, st = _lib.load(), _lib.stream_ptr()
+        B, n, o = self.B, self.n, self.loss_out
+        _lib.check(lib.clica_dot_loss_fwd_train(C.byref(self.desc), y1.data_ptr(), n, y2.data_ptr(), n, pool.data_ptr(), n,
+                                                o[:B].data_ptr(), o[B:2 * B].data_ptr(), lse.data_ptr(),
+                                                self.dy[:B].data_ptr(), n, self.dy[B:].data_ptr(), n,
+                                                self.loss_ws.data_ptr(), self.loss_ws.numel(), st), "clica_dot_loss_fwd_train")
+        pool_lse = self._pooled(lse, self.lse_all)
+        self.handoff.dy_parts = None
+        _lib.check(lib.clica_dot_loss_bwd_sym_train(C.byref(self.desc), y1.data_ptr(), n, pool.data_ptr(), n,
+                                                    lse.data_ptr(), pool_lse.data_ptr(), self.dy[:B].data_ptr(), n, o[3 * B:].data_ptr(),
+                                                    tick, self.loss_ws.data_ptr(), self.loss_ws.numel(), st), "clica_dot_loss_bwd_sym_train")
+        self.handoff.ticked = self.early_tick
+
+    def _loss_state(self):
+        return ops.lp_loss_train_state_export(self.desc, self.loss_ws) if (self.loss_train and not self.dot) else None
+
+    def _load_loss_state(self, blob):
+        if self.loss_train and not self.dot:
+            ops.lp_loss_train_state_import(self.desc, self.loss_ws, blob)
+
+
     def loss_spread(self) -> float:
         """M = log2(e)/tau max_i |y_i - y_0|^2 of the largest embedding cloud the p = 2 matrix-core loss sweeps have seen in this
         trainer (0 on the VALU sweeps): their logit error scales with it (include/clica.h).  Host read + sync -- for
@@ -1252,12 +1286,9 @@ class ContrastiveTrainer:
                     encoder_path="whole-stack" if self.fused_forward else "per-layer", split_bf16=bool(self.split_bf16),
                     graph_captured=self.graph is not None)
 
-    @property
-    def steps_done(self) -> int:
-        return int(self.step_dev.item())
 
 
-class SupervisedTrainer(ContrastiveTrainer):
+class SupervisedTrainer(_FusedTrainer):
     """Fused, HBM-resident step of the SUPERVISED phase of main_mlp.py (the first of the default ``test_list = [True, False]``,
     :249-255): ``F.mse_loss(f(g(z1)), z1)`` (:274-276), backward, Adam -- no autograd, no host sync.
 
@@ -1273,20 +1304,12 @@ class SupervisedTrainer(ContrastiveTrainer):
     fold_mse = True
     _kind = "supervised"
 
-    def __init__(self, f: nn.Sequential, g_weights: torch.Tensor, sampler: SamplerSpec, batch_size: int,
-                 lr: float = 1e-4, g_slope: float = 0.2, betas=(0.9, 0.999), eps: float = 1e-8, device=None,
-                 process_group: Optional[dist.ProcessGroup] = None, bucket_bytes: int = 8 << 20,
-                 force_collectives: bool = False, overlap_backward: bool = True, fused_forward: bool = True,
-                 split_bf16: Optional[bool] = None, g_act_kind: int = 0, emulate_pool_ranks: int = 1, dry_ranks: int = 1,
-                 split_arith: Optional[str] = None):
-        world = dist.get_world_size(process_group) if dist.is_initialized() else 1
-        if world > 1 or force_collectives or int(dry_ranks) > 1 or int(emulate_pool_ranks) > 1:
+    def __init__(self, f: nn.Sequential, g_weights: torch.Tensor, sampler: SamplerSpec, batch_size: int, lr: float = 1e-4, **engine):
+        world = dist.get_world_size(engine.get("process_group")) if dist.is_initialized() else 1
+        if world > 1 or engine.get("force_collectives") or max(int(engine.get(k, 1)) for k in ("dry_ranks", "emulate_pool_ranks")) > 1:
             raise NotImplementedError("SupervisedTrainer runs on one rank: data parallelism of the supervised step is not implemented "
                                       "(train_mlp runs that phase through autograd_train_step when world > 1)")
-        super().__init__(f, g_weights, sampler, batch_size, p=2, lr=lr, g_slope=g_slope, betas=betas, eps=eps, device=device,
-                         process_group=process_group, bucket_bytes=bucket_bytes, overlap_backward=overlap_backward,
-                         fused_forward=fused_forward, split_bf16=split_bf16, g_act_kind=g_act_kind, split_arith=split_arith)
-        self.p = self.tau = self.alpha = None        # (no contrastive loss in this step)
+        super().__init__(f, g_weights, sampler, batch_size, lr=lr, **engine)
 
     def _enc_rows(self) -> int:
         return self.B
@@ -1295,45 +1318,34 @@ class SupervisedTrainer(ContrastiveTrainer):
         f32 = dict(dtype=torch.float32, device=self.device)
         self.dy = torch.empty((R, self.n), **f32)
         self.loss_out = torch.zeros(1, **f32)
-        self.z_all = self.lse_all = self.desc = None
-        self.loss_train = False
         self.loss_ws = ops.mse_loss_workspace(R, self.n, self.device)     # arrival counter + partials (zero between launches)
         self.early_tick = True           # the objective's launch (or the chain's prologue) advances the step / RNG counter
-        self._ticked = False
-        self._mse_fold = None
+
+    def _objective_folds(self, on_dy: bool):
+        return False, on_dy and self.fold_mse
 
     def inject(self, z1: torch.Tensor, z2: Optional[torch.Tensor] = None):
         """Use caller-provided latents z1 (parity tests); `z2` is accepted for symmetry with the contrastive step and not used."""
         self.z[:self.B].copy_(z1)
         self._mix()
 
-    def step_injected(self, z1, z2=None):
-        return super().step_injected(z1, z2)
-
     def _result(self) -> torch.Tensor:
         return self.loss_out
 
-    def _chain_takes_mse(self) -> bool:
-        """Will THIS step's backward chain run with its tail directly on dY?  Then its prologue forms dY and the loss."""
-        if not self.fold_mse or not getattr(self, "_in_step", False):
-            return False
-        if self.head is not None or not (self.split_bf16 and self.split_wgrad and self.fused_backward):
-            return False
-        return self._adam_folds_into_wgrad() and self._chain_tail_ok()
-
     def loss_forward_backward(self):
         """loss = mean((y - z1)^2), dY = 2 (y - z1) / (B n): left to the backward chain's prologue, or one launch here."""
-        target = self.z[:self.B]
+        target, h = self.z[:self.B], self.handoff
         tick = self.step_dev if self.early_tick else None
-        self._mse_fold = None
-        if self._chain_takes_mse():
-            self._mse_fold = dict(y=self.y, target=target, loss_out=self.loss_out, ws=self.loss_ws, tick=tick)
-            self._mse_taken = getattr(self, "_mse_taken", 0) + 1       # (tests: which path a trainer took)
+        h.mse = None
+        if h.in_step and self.plan.mse_in_chain:
+            h.mse = dict(y=self.y, target=target, loss_out=self.loss_out, ws=self.loss_ws, tick=tick)
+            self._mse_taken += 1
         else:
             ops.mse_loss_fwd_bwd(self.y, target, dy=self.dy, loss_out=self.loss_out, ws=self.loss_ws, tick_counter=tick)
-        self._ticked = self.early_tick
+        h.ticked = self.early_tick
 
     def loss_spread(self) -> float:
+        """(train_mlp asks every trainer at its log points: the MSE objective has no spread guard)"""
         return 0.0
 
     def plan_summary(self) -> dict:

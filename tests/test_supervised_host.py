@@ -66,7 +66,12 @@ def test_supervised_trainer_is_public_and_refuses_data_parallelism():
     import torch
     from cl_ica_amd import engine
     from cl_ica_amd.engine import SamplerSpec, SupervisedTrainer
-    assert "SupervisedTrainer" in engine.__all__ and issubclass(SupervisedTrainer, engine.ContrastiveTrainer)
+    assert "SupervisedTrainer" in engine.__all__
+    # the two objectives are siblings on the shared step machinery: neither carries the other's loss
+    shared = set(SupervisedTrainer.__mro__) & set(engine.ContrastiveTrainer.__mro__) - {object}
+    assert shared and not issubclass(SupervisedTrainer, engine.ContrastiveTrainer)
+    assert all(hasattr(c, "step") and hasattr(c, "capture") and hasattr(c, "load_state_dict") for c in shared)
+    assert not hasattr(SupervisedTrainer, "loss_guard") and SupervisedTrainer.loss_spread(None) == 0.0
     f = torch.nn.Sequential(torch.nn.Linear(4, 4))
     with pytest.raises(NotImplementedError, match="one rank"):
         SupervisedTrainer(f, torch.eye(4).repeat(3, 1, 1), SamplerSpec(n=4), batch_size=8, device="cpu", force_collectives=True)

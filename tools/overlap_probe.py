@@ -60,7 +60,7 @@ def loss_two_calls(between):
     _lib.check(lib.clica_lp_loss_bwd_sym_train(C.byref(tr.desc), y1.data_ptr(), n, y1.data_ptr(), n, lse.data_ptr(), lse.data_ptr(),
                                                tr.dy[:B].data_ptr(), n, o[3 * B:].data_ptr(), tr.step_dev.data_ptr() if tr.early_tick else None,
                                                tr.loss_ws.data_ptr(), tr.loss_ws.numel(), _lib.stream_ptr()), "bwd_sym_train")
-    tr._ticked = tr.early_tick
+    tr.handoff.ticked = tr.early_tick
 
 
 def body(variant):

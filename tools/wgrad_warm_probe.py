@@ -27,11 +27,11 @@ def timed(fn, reps=20):
 import inspect
 src = inspect.getsource(tr.backward)
 gg = tr._head_backward()
-tr._fold_adam = tr._adam_folds_into_wgrad()
+tr.handoff.fold_adam = tr._adam_folds_into_wgrad()
 def wg():
-    tr._tail_ready = False
+    tr.handoff.tail_ready = False
     tr.weight_grads(gg)
-print("fold_adam", tr._fold_adam)
+print("fold_adam", tr.handoff.fold_adam)
 print(f"weight gradients + slab reduction, back to back on the same operands: {timed(wg):.1f} us per call")
 big = torch.empty(1 << 28, dtype=torch.uint8, device="cuda")     # 256 MB: evict the operands between the calls
 def wg_cold():
