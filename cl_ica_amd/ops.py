@@ -1073,6 +1073,64 @@ def kitti_gather_pairs(frames: torch.Tensor, first: torch.Tensor, second: torch.
     return images, labels
 
 
+def _image_table(table: torch.Tensor) -> Tuple[int, int, int, int]:
+    if not torch.is_tensor(table):
+        raise ValueError("table must be a uint8 tensor [N, H, W, C]")
+    if not table.is_cuda:
+        raise ClicaError(f"table must live on the GPU (got device {table.device}); cl_ica_amd runs only through its HIP kernels")
+    if table.dtype != torch.uint8 or not table.is_contiguous() or table.dim() != 4:
+        raise ValueError(f"table must be a contiguous uint8 tensor [N, H, W, C] (got {table.dtype}, shape {tuple(table.shape)})")
+    N, H, W, Cn = table.shape
+    if N == 0 or H == 0 or W == 0:
+        raise ValueError(f"table of shape {tuple(table.shape)} holds no pixels")
+    if not 1 <= Cn <= 4:
+        raise ValueError(f"table has C={Cn} channels (1..4 supported)")
+    return N, H, W, Cn
+
+
+def _host_floats(name: str, v, n: int):
+    v = v.detach().cpu().tolist() if torch.is_tensor(v) else list(v)
+    if len(v) != n:
+        raise ValueError(f"{name} has {len(v)} entries for C={n} channels")
+    return (C.c_float * n)(*[float(e) for e in v])
+
+
+def image_gather_norm(table: torch.Tensor, index: torch.Tensor, mean=None, std=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """float32 batch [len(index), C, H, W] of the rows `index` of a uint8 image table [N, H, W, C] in HBM, one launch
+    (clica_image_gather_norm): ``((v / 255) - mean[c]) / std[c]``, torchvision's ToTensor + Normalize (main_3dident.py:787-796) as three
+    correctly rounded fp32 operations; ``mean is std is None``: ToTensor alone.  `mean` / `std` are host sequences of C numbers, read at
+    the call.  `out`: a float32 buffer of that shape to write into (a captured graph keeps its buffer; `index` is then read on replay)."""
+    N, H, W, Cn = _image_table(table)
+    if (mean is None) != (std is None):
+        raise ValueError("mean and std must be given together")
+    m = s = None
+    if mean is not None:
+        m, s = _host_floats("mean", mean, Cn), _host_floats("std", std, Cn)
+    if not (torch.is_tensor(index) and index.device == table.device and index.dtype == torch.int64 and index.is_contiguous()):
+        index = torch.as_tensor(index).to(device=table.device, dtype=torch.int64).contiguous()
+    n = index.numel()
+    if n == 0 or index.dim() != 1:
+        raise ValueError(f"index must be a non-empty 1-D list of rows (got shape {tuple(index.shape)})")
+    if out is None:
+        out = torch.empty((n, Cn, H, W), dtype=torch.float32, device=table.device)
+    else:
+        require_cuda(out, "out")
+        if tuple(out.shape) != (n, Cn, H, W) or not out.is_contiguous() or out.device != table.device:
+            raise ValueError(f"out must be a contiguous float32 tensor {(n, Cn, H, W)} on {table.device} (got {tuple(out.shape)})")
+    check(load().clica_image_gather_norm(table.data_ptr(), N, H, W, Cn, index.data_ptr(), n, m, s, out.data_ptr(), stream_ptr()),
+          "clica_image_gather_norm")
+    return out
+
+
+def image_channel_sums(table: torch.Tensor) -> torch.Tensor:
+    """Exact integer sums per image and channel of a uint8 table [N, H, W, C] (clica_image_channel_stats): int64 [N, C, 2] on the device,
+    ``[..., 0]`` = sum of the bytes, ``[..., 1]`` = sum of their squares (the data pass of tools/3dident/get_mean_std.py)."""
+    N, H, W, Cn = _image_table(table)
+    sums = torch.empty((N, Cn, 2), dtype=torch.int64, device=table.device)      # (uint64 in the ABI; the sums stay far below 2^63)
+    check(load().clica_image_channel_stats(table.data_ptr(), N, H, W, Cn, sums.data_ptr(), stream_ptr()), "clica_image_channel_stats")
+    return sums
+
+
 def moments(a: torch.Tensor, b: Optional[torch.Tensor] = None) -> torch.Tensor:
     """G = [a | b | 1]^T [a | b | 1] in fp64 (clica_moments): the (da + db + 1)^2 second-moment matrix every disentanglement score is a
     function of (cl_ica_amd/disentanglement_utils.py).  a [M, da], b [M, db] fp32 on the device; returns a device fp64 tensor."""

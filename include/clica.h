@@ -44,7 +44,8 @@ const char* clica_last_error(void);
  * generic fused epilogue instead of the one specialised per output combination), "lp_fused_finalize" (0: clica_lp_loss_fwd_train as sweep +
  * finalize launch), "lp_max_splits" (k > 0: the Lp / dot loss sweeps and clica_nn_search cut their stream into at most k splits, in the
  * launches and in the workspace sizes alike -- set it before the workspace query; with k = 1 a pool of a few hundred rows is several
- * on-chip tiles per workgroup, which the product plan only reaches from B ~ 2500 on; 0: no cap, the default), "reset" (all defaults).  Unknown key: CLICA_E_INVALID.  The library
+ * on-chip tiles per workgroup, which the product plan only reaches from B ~ 2500 on; 0: no cap, the default), "image_nt_stores" (0:
+ * clica_image_gather_norm's RGB path writes its planes with plain stores; same bits; 1, the default: non-temporal stores), "reset" (all defaults).  Unknown key: CLICA_E_INVALID.  The library
  * reads NO tuning switch from the environment (the environment variables it does read are listed in INTEGRATION.md). */
 int clica_set_tuning(const char* key, int32_t value);
 /* After a FAILED stream capture on `stream` (e.g. a collective that cannot be captured): end the capture if the stream is
@@ -832,6 +833,25 @@ int clica_nn_search(const float* table, int64_t ldt, int64_t n_table, const floa
 int clica_kitti_gather_pairs(const uint8_t* frames, int64_t frame_elems, int64_t n_frames, const int64_t* first_frame,
                              const int64_t* second_frame, int64_t n_pairs, float* images, const float* latents, int32_t n_latents,
                              float* labels, clica_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Image batches from a uint8 table in HBM  --  the image half of ThreeDIdentDataset / SequentialThreeDIdentDataset
+ * (datasets/threedident_dataset.py:120-127, 184-190) under the transform of main_3dident.py:787-796 (torchvision ToTensor, then Normalize):
+ *   out[i][c][y][x] = ((float(table[index[i]][y][x][c]) / 255.0f) - mean[c]) / std[c]
+ * as three correctly rounded fp32 operations (two divisions, one subtraction), so the result is defined bit for bit.
+ * table: uint8 [n_images][H][W][C] on the device (the interleaved layout PIL decodes to); index: int64 [n_index] on the device, clamped to
+ * 0 .. n_images - 1 by the kernel; out: fp32 [n_index][C][H][W] on the device.  mean / std: HOST arrays of C floats read at the call and
+ * passed to the kernel by value (a captured launch keeps the values it was recorded with); both NULL: ToTensor alone.  1 <= C <= 4.
+ * C == 3 with H W a multiple of 4 takes the vector path (table 4-byte, out 16-byte aligned); every other shape one pixel per thread
+ * (out 4-byte aligned).  One launch; both views of a pair batch are gathered by passing the 2 B concatenated indices.
+ * clica_image_channel_stats: sums[i][c][0] = sum of the bytes of channel c of image i, sums[i][c][1] = sum of their squares (uint64
+ * [n_images][C][2], exact integers; one workgroup per image, fixed-order combine, no atomics)  --  the data pass of
+ * tools/3dident/get_mean_std.py; the mean / unbiased std are finished from them on the host in fp64.
+ * ---------------------------------------------------------------------------------- */
+int clica_image_gather_norm(const uint8_t* table, int64_t n_images, int32_t H, int32_t W, int32_t C, const int64_t* index,
+                            int64_t n_index, const float* mean, const float* std, float* out, clica_stream_t stream);
+int clica_image_channel_stats(const uint8_t* table, int64_t n_images, int32_t H, int32_t W, int32_t C, uint64_t* sums,
+                              clica_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Second moments for the disentanglement scores  --  replaces the host-side sklearn / numpy / scipy passes of
