@@ -976,6 +976,96 @@ def groupnorm_lrelu_bwd(x, y, dy, weight, mean, rstd, slope: float = 0.01):
     return dx, dw, db
 
 
+# ------------------------------------------------------------------------------- BatchNorm2d (+ residual) + (leaky) ReLU, NCHW
+# partial workspaces of the bn2d kernels per (device, N, C, HW); as _NORM_WS an entry is never replaced or freed, so a pointer a captured
+# graph recorded stays valid.  No initial contents are needed; one entry serves one launch at a time on one stream.
+_BN2D_WS = {}
+
+
+def bn2d_workspace(N: int, C_: int, HW: int, device) -> torch.Tensor:
+    """The cached workspace of clica_bn2d_act_fwd_train / _bwd for x[N, C, H, W] with H W = HW on `device`."""
+    device = torch.device(device)
+    key = (device.index if device.index is not None else torch.cuda.current_device(), int(N), int(C_), int(HW))
+    ws = _BN2D_WS.get(key)
+    if ws is None:
+        nb = C.c_size_t()
+        check(load().clica_bn2d_workspace_bytes(int(N), int(C_), int(HW), C.byref(nb)), "clica_bn2d_workspace_bytes")
+        if torch.cuda.is_current_stream_capturing():
+            # (memory allocated while capturing belongs to the graph's pool: not something to cache)
+            raise ClicaError(f"bn2d: no workspace for shape ({N}, {C_}, {HW}) yet -- run the step once eagerly before capturing it")
+        ws = _BN2D_WS[key] = torch.empty(max(nb.value, 16), dtype=torch.uint8, device=device)
+    _lib.note_graph_use(ws)
+    return ws
+
+
+def _bn2d_map(name: str, t: torch.Tensor, shape=None) -> torch.Tensor:
+    if t.dim() != 4 or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous NCHW tensor [N, C, H, W], got shape {tuple(t.shape)} strides {t.stride()}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} {tuple(t.shape)} must have the shape of x {tuple(shape)}")
+    require_cuda(t, name)
+    return t
+
+
+def batchnorm2d_act_fwd(x, weight, bias, running_mean=None, running_var=None, eps: float = 1e-5, momentum: float = 0.1,
+                        slope: float = 0.0, residual=None):
+    """Training BatchNorm2d of contiguous NCHW x (N H W >= 2), plus `residual` when given, then LeakyReLU(slope) (0: ReLU, 1: none) in
+    two launches (clica_bn2d_act_fwd_train); running_mean / running_var, when given, are updated in place as nn.BatchNorm2d does.
+    Returns (y, save_mean [C], save_invstd [C]); the last two are what batchnorm2d_act_bwd needs."""
+    x = _bn2d_map("x", x)
+    N, n, H, W = x.shape
+    if residual is not None:
+        _bn2d_map("residual", residual, x.shape)
+    _norm_vec("weight", weight, n); _norm_vec("bias", bias, n)
+    if (running_mean is None) != (running_var is None):
+        raise ValueError("running_mean and running_var come together")
+    if running_mean is not None:
+        _norm_vec("running_mean", running_mean, n); _norm_vec("running_var", running_var, n)
+    ws = bn2d_workspace(N, n, H * W, x.device)       # (validates the shape)
+    y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    save_mean = torch.empty(n, dtype=torch.float32, device=x.device)
+    save_invstd = torch.empty(n, dtype=torch.float32, device=x.device)
+    check(load().clica_bn2d_act_fwd_train(x.data_ptr(), ptr(residual), weight.data_ptr(), bias.data_ptr(), N, n, H * W, float(eps),
+                                          float(momentum), float(slope), y.data_ptr(), save_mean.data_ptr(), save_invstd.data_ptr(),
+                                          ptr(running_mean), ptr(running_var), ws.data_ptr(), ws.numel(), stream_ptr()),
+          "clica_bn2d_act_fwd_train")
+    return y, save_mean, save_invstd
+
+
+def batchnorm2d_act_eval(x, weight, bias, running_mean, running_var, eps: float = 1e-5, slope: float = 0.0, residual=None):
+    """Inference BatchNorm2d on the running statistics, plus `residual` when given, then LeakyReLU(slope): one element-wise launch
+    (clica_bn2d_act_fwd_eval)."""
+    x = _bn2d_map("x", x)
+    N, n, H, W = x.shape
+    if residual is not None:
+        _bn2d_map("residual", residual, x.shape)
+    for nm, t in (("weight", weight), ("bias", bias), ("running_mean", running_mean), ("running_var", running_var)):
+        _norm_vec(nm, t, n)
+    y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    check(load().clica_bn2d_act_fwd_eval(x.data_ptr(), ptr(residual), weight.data_ptr(), bias.data_ptr(), running_mean.data_ptr(),
+                                         running_var.data_ptr(), N, n, H * W, float(eps), float(slope), y.data_ptr(), stream_ptr()),
+          "clica_bn2d_act_fwd_eval")
+    return y
+
+
+def batchnorm2d_act_bwd(x, y, dy, weight, save_mean, save_invstd, slope: float = 0.0, need_dr: bool = False):
+    """(dx, dr, dweight, dbias) of batchnorm2d_act_fwd from its input x, its OUTPUT y (the gate) and the saved statistics: two launches
+    (clica_bn2d_act_bwd).  dr, the residual's gradient dy gate(y), is None unless `need_dr`."""
+    x = _bn2d_map("x", x)
+    _bn2d_map("y", y, x.shape); _bn2d_map("dy", dy, x.shape)
+    N, n, H, W = x.shape
+    _norm_vec("weight", weight, n); _norm_vec("save_mean", save_mean, n); _norm_vec("save_invstd", save_invstd, n)
+    ws = bn2d_workspace(N, n, H * W, x.device)
+    dx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    dr = torch.empty(x.shape, dtype=torch.float32, device=x.device) if need_dr else None
+    dw = torch.empty(n, dtype=torch.float32, device=x.device)
+    db = torch.empty(n, dtype=torch.float32, device=x.device)
+    check(load().clica_bn2d_act_bwd(x.data_ptr(), y.data_ptr(), dy.data_ptr(), weight.data_ptr(), save_mean.data_ptr(),
+                                    save_invstd.data_ptr(), N, n, H * W, float(slope), dx.data_ptr(), ptr(dr), dw.data_ptr(), db.data_ptr(),
+                                    ws.data_ptr(), ws.numel(), stream_ptr()), "clica_bn2d_act_bwd")
+    return dx, dr, dw, db
+
+
 def tick(counter: torch.Tensor):
     check(load().clica_tick(counter.data_ptr(), stream_ptr()), "clica_tick")
 

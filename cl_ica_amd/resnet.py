@@ -5,14 +5,82 @@ The 3DIdent driver builds its encoder as ``torchvision.models.resnet18(False, nu
 back to this module when the import fails: the same architecture (7x7 stem, max-pool, four stages of two basic blocks, global
 average pool, fc) and the same attribute names -- ``conv1, bn1, layer1..4[.i].{conv1,bn1,conv2,bn2,downsample.{0,1}}, fc`` -- so a
 state dict written by torchvision's model loads here and vice versa.  The convolutions run on PyTorch-ROCm / MIOpen, as BASELINE
-config 4 prescribes ("conv path via PyTorch-ROCm + HIP loss"); nothing here is device code of ours.
+config 4 prescribes ("conv path via PyTorch-ROCm + HIP loss").
+
+Everything between the convolutions -- BatchNorm2d, the shortcut add, the ReLU -- is one call of the fused kernels of csrc/bn2d.hip per
+unit (``bn1 + relu``, ``bn2 (+ shortcut) + relu``, ``downsample[1]``) whenever ``_bn2d_on_hip`` holds: NORM_MODE "hip", a contiguous
+(NCHW) fp32 CUDA input, an affine module that tracks running statistics with a momentum, in training or in inference outside autograd.
+Anything else -- channels-last inputs among it -- runs the modules' own forward and torch's ``relu`` / ``+``.  The modules stay plain
+``nn.BatchNorm2d`` objects that own weight, bias, running_mean, running_var and num_batches_tracked: the state dict does not change.
 """
 from __future__ import annotations
 
+import os
+
 import torch
 from torch import nn
+from torch.autograd.function import once_differentiable
+
+from . import ops
 
 __all__ = ["resnet18", "ResNet18", "BasicBlock"]
+
+# "hip": the fused kernels where they apply; "torch": the modules' own forward everywhere (the A/B leg).  Read at call time.
+NORM_MODE = os.environ.get("CLICA_RESNET_NORM", "hip")
+if NORM_MODE not in ("hip", "torch"):
+    raise ValueError(f"CLICA_RESNET_NORM={NORM_MODE!r} (one of 'hip', 'torch')")
+
+
+class _BN2dActFn(torch.autograd.Function):
+    """nn.BatchNorm2d in training mode + the shortcut add + the ReLU behind it (slope = 1: none) on clica_bn2d_act_fwd_train / _bwd.
+    `mod` is the module itself: its running statistics are updated in place by the forward's second launch, as its own forward does."""
+
+    @staticmethod
+    def forward(ctx, x, r, weight, bias, mod, slope):
+        y, save_mean, save_invstd = ops.batchnorm2d_act_fwd(x, weight, bias, mod.running_mean, mod.running_var, mod.eps, mod.momentum, slope,
+                                                            residual=r)
+        ctx.save_for_backward(x, y, weight, save_mean, save_invstd)
+        ctx.slope = slope
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x, y, weight, save_mean, save_invstd = ctx.saved_tensors
+        dx, dr, dw, db = ops.batchnorm2d_act_bwd(x, y, gy.contiguous(), weight, save_mean, save_invstd, ctx.slope,
+                                                 need_dr=ctx.needs_input_grad[1])
+        return dx, dr, dw, db, None, None
+
+
+def _bn2d_on_hip(m, x, r=None) -> bool:
+    """Do the bn2d kernels cover this module on this input (and residual)?  Anything else runs the module's own forward, as before."""
+    if NORM_MODE != "hip" or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
+        return False
+    if r is not None and not (r.is_cuda and r.dtype == torch.float32 and r.shape == x.shape and r.is_contiguous()):
+        return False
+    if not (isinstance(m, nn.BatchNorm2d) and m.affine and m.track_running_stats and m.momentum is not None and x.shape[1] == m.num_features):
+        return False
+    if m.training:
+        if x.shape[0] * x.shape[2] * x.shape[3] < 2:        # (the module's own error to raise)
+            return False
+    elif torch.is_grad_enabled():                           # inference inside autograd: the module's own forward
+        return False
+    return m.weight.is_cuda and m.weight.dtype == torch.float32
+
+
+def _unit(bn, relu, x, r=None):
+    """relu(bn(x) + r) -- `relu` None: no activation, `r` None: no shortcut -- as one fused call where the kernels apply."""
+    if not _bn2d_on_hip(bn, x, r):
+        y = bn(x)
+        if r is not None:
+            y = y + r
+        return y if relu is None else relu(y)
+    slope = 1.0 if relu is None else 0.0
+    if bn.training:
+        ops.bn2d_workspace(x.shape[0], x.shape[1], x.shape[2] * x.shape[3], x.device)   # (raises while capturing without a warm-up: before anything is counted)
+        bn.num_batches_tracked.add_(1)                      # in place on the device: capturable
+        return _BN2dActFn.apply(x, r, bn.weight, bn.bias, bn, slope)
+    return ops.batchnorm2d_act_eval(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.eps), slope, residual=r)
 
 
 class BasicBlock(nn.Module):
@@ -30,9 +98,13 @@ class BasicBlock(nn.Module):
             self.downsample = nn.Sequential(nn.Conv2d(inplanes, planes, 1, stride, bias=False), nn.BatchNorm2d(planes))
 
     def forward(self, x):
-        y = self.relu(self.bn1(self.conv1(x)))
-        y = self.bn2(self.conv2(y))
-        return self.relu(y + (x if self.downsample is None else self.downsample(x)))
+        if NORM_MODE != "hip":
+            y = self.relu(self.bn1(self.conv1(x)))
+            y = self.bn2(self.conv2(y))
+            return self.relu(y + (x if self.downsample is None else self.downsample(x)))
+        y = _unit(self.bn1, self.relu, self.conv1(x))
+        identity = x if self.downsample is None else _unit(self.downsample[1], None, self.downsample[0](x))
+        return _unit(self.bn2, self.relu, self.conv2(y), identity)
 
 
 class ResNet18(nn.Module):
@@ -56,7 +128,7 @@ class ResNet18(nn.Module):
                 nn.init.constant_(m.bias, 0)
 
     def forward(self, x):
-        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+        x = self.maxpool(self.relu(self.bn1(self.conv1(x))) if NORM_MODE != "hip" else _unit(self.bn1, self.relu, self.conv1(x)))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         return self.fc(torch.flatten(self.avgpool(x), 1))
 

@@ -689,6 +689,34 @@ int clica_gn_lrelu_bwd(const float* X, const float* Y, const float* dY, const fl
                        int64_t M, int32_t C, float slope, float* dX, float* dgamma, float* dbeta, void* workspace,
                        size_t workspace_bytes, clica_stream_t stream);
 
+/* BatchNorm2d fused with the shortcut add and the (leaky) ReLU behind it: the normalisation units of the ResNet-18 backbone
+ * (cl_ica_amd/resnet.py).  fp32, CONTIGUOUS NCHW X[N, C, HW] (HW = H W), statistics over the N HW values of a channel:
+ *   Z = gamma[c] (X - mean[c]) invstd[c] + beta[c] (+ R when a residual of the same shape and layout is given),
+ *   Y = Z > 0 ? Z : slope Z;  slope = 0: ReLU, slope = 1: no activation (the downsample branch), slope < 0 is refused
+ *   (the backward takes its gate from the saved output Y: Y > 0 -> 1, else slope; Z is never recomputed).
+ * Training (N HW >= 2): biased batch variance, invstd = 1 / sqrt(M2 / (N HW) + eps); save_mean[C] / save_invstd[C] are what the
+ *   backward needs; running_mean / running_var (NULL: do not track) become (1 - momentum) running + momentum (mean | M2 / (N HW - 1)).
+ *   Two launches: Welford / Chan partials of X minus the channel's first value per (image split, channel) into the workspace, then an
+ *   apply launch in which every workgroup merges the partials of its channel in split order.  Backward, two launches of the same shape:
+ *   dZ = dY gate(Y), dR = dZ (NULL: not wanted), dX = gamma invstd (dZ - sum dZ / M - xhat sum(dZ xhat) / M), dgamma = sum dZ xhat,
+ *   dbeta = sum dZ.  Inference: one element-wise launch on the running statistics.
+ * All element offsets are 64-bit.  HW % 4 == 0 with 16-byte aligned tensors moves 16 bytes per lane and access; any other HW, or an
+ * unaligned pointer, takes scalar accesses (for HW % 4 == 0 in the same reduction order: the same bits).
+ * No floating-point atomics, no in-kernel counters: eager launches and graph replays give the same bits.  The workspace
+ * (clica_bn2d_workspace_bytes, 16-byte aligned, no initial contents needed) serves one call at a time.  clica_bn2d_workspace_bytes is
+ * host-only and validates a shape: -1 for N HW < 2, C < 1, bytes == NULL. */
+int clica_bn2d_workspace_bytes(int64_t N, int32_t C, int32_t HW, size_t* bytes);
+int clica_bn2d_act_fwd_train(const float* X, const float* R /*or NULL*/, const float* gamma, const float* beta, int64_t N, int32_t C,
+                             int32_t HW, float eps, float momentum, float slope, float* Y, float* save_mean, float* save_invstd,
+                             float* running_mean /*[C] or NULL*/, float* running_var /*[C] or NULL*/, void* workspace,
+                             size_t workspace_bytes, clica_stream_t stream);
+int clica_bn2d_act_fwd_eval(const float* X, const float* R /*or NULL*/, const float* gamma, const float* beta, const float* running_mean,
+                            const float* running_var, int64_t N, int32_t C, int32_t HW, float eps, float slope, float* Y,
+                            clica_stream_t stream);
+int clica_bn2d_act_bwd(const float* X, const float* Y, const float* dY, const float* gamma, const float* save_mean,
+                       const float* save_invstd, int64_t N, int32_t C, int32_t HW, float slope, float* dX, float* dR /*or NULL*/,
+                       float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, clica_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Convolution stack of the KITTI-masks encoder  --  BetaVAE_H, /root/reference/kitti_masks/model.py:41-56:
  * Conv2d(k = 4, stride 2, pad 1) + ReLU stages as implicit GEMMs (fp32 MFMA, csrc/linear.hip, conv section), channels-last.
