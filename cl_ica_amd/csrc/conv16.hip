@@ -146,6 +146,9 @@ __global__ __launch_bounds__(256) void amax_k(const float* __restrict__ x, int64
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
     const float4 v = reinterpret_cast<const float4*>(x)[i];
     m = fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+    // fmaxf drops a NaN operand: the sum keeps it (or makes one of inf - inf), and the maximum becomes inf -> commit_amax's huge value
+    const float t = (v.x + v.y) + (v.z + v.w);
+    m = (t != t) ? __builtin_inff() : m;
   }
   commit_amax(slots, m, blockIdx.x * 4 + (threadIdx.x >> 6));
 }
@@ -1104,10 +1107,14 @@ void launch_slab_sum(const float* slab1, int n1, float* out1, const float* slab2
 }
 
 struct WPlan { int splits; int64_t rows_per_split; };
-static WPlan plan_wgrad(int64_t prows, int C4) {
+// contraction splits the planner aims for: non-decreasing in prows, and plan_wgrad never makes more than this many
+static int64_t want_wgrad(int64_t prows, int C4) {
   const int ctiles = C4 / WG_COLS;
-  int64_t want = std::max<int64_t>(1, 2 * (int64_t)kNumCU / ctiles);       // ~two eight-wave workgroups per CU
-  want = std::min<int64_t>(want, std::max<int64_t>(1, prows / (4 * WG_ROWS)));
+  const int64_t want = std::max<int64_t>(1, 2 * (int64_t)kNumCU / ctiles);  // ~two eight-wave workgroups per CU
+  return std::min<int64_t>(want, std::max<int64_t>(1, prows / (4 * WG_ROWS)));
+}
+static WPlan plan_wgrad(int64_t prows, int C4) {
+  const int64_t want = want_wgrad(prows, C4);
   WPlan p;
   p.rows_per_split = ceil_div(ceil_div(prows, want), (int64_t)WG_ROWS) * WG_ROWS;
   p.splits = (int)ceil_div(prows, p.rows_per_split);
@@ -1197,8 +1204,12 @@ extern "C" int clica_conv16_k4s2_dgrad(const float* dO, const uint16_t* WdT16, c
 
 extern "C" int clica_conv16_k4s2_wgrad_workspace_bytes(int64_t rows, int32_t Cout, int32_t K, size_t* bytes) {
   CLICA_CHECK_ARG(bytes && rows > 0 && Cout >= 1 && K >= 4 * WG_COLS && K % (4 * WG_COLS) == 0, "clica_conv16_k4s2_wgrad_workspace_bytes: bad argument");
-  const WPlan p = plan_wgrad(rows + 4 * 1024, K / 4);      // an upper bound over the grid widths (prows = rows + ws + 1)
-  *bytes = align_up((size_t)(p.splits + 2) * Cout * K * sizeof(float), 256) + align_up((size_t)(p.splits + 2) * Cout * sizeof(float), 256);
+  // The call plans with prows = rows + ws + 1 <= rows + 4096 (it refuses ws >= 4096) and makes splits <= want_wgrad(prows): rows_per_split
+  // >= prows / want.  The split COUNT is not monotone in prows (the rounding of rows_per_split to whole steps), want_wgrad is: granting
+  // want_wgrad(rows + 4096) slabs covers every grid width.  (plan_wgrad(rows + 4096).splits + 2 did not: 393 slabs asked against 342
+  // granted for the 17 x 17 stage at 174 images.)
+  const size_t slabs = (size_t)want_wgrad(rows + 4 * 1024, K / 4);
+  *bytes = align_up(slabs * Cout * K * sizeof(float), 256) + align_up(slabs * Cout * sizeof(float), 256);
   return CLICA_OK;
 }
 
