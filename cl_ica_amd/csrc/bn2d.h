@@ -50,5 +50,99 @@ static inline size_t workspace_bytes(int64_t N, int32_t C, int32_t HW) {
   return align_up((size_t)3 * (size_t)geometry(N, HW).S * (size_t)C * sizeof(float), 16);
 }
 
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// ------------------------------------------------------------------------------------------------ stem unit with the max-pool (pool2d.hip)
+// P = maxpool 3x3 / stride 2 / pad 1 of lrelu(gamma xhat + beta), floor mode.  The plane decomposition above: one workgroup =
+// (channel, image split); it sweeps its split's planes in batches of as many whole planes as fit kPoolLdsFloats: a batch's planes
+// [H][W] sit in LDS back to back, in the backward followed by the batch's gated window gradients [Ho][Wo] and a nibble per window (the
+// position of its first maximum).  Hence the limit on a plane: pool_lds_floats(H, W) = H W + Ho Wo + ceil(Ho Wo / 8) <= kPoolLdsFloats
+// (112 x 112 with its 56 x 56 windows fits exactly: 64288 of the 65536 bytes of static LDS).
+// Planes with pool_lds_floats <= kPoolLdsSmall (the 32 x 32 stem planes of 64 x 64 images among them) run instances with 16 KB of LDS, so
+// that eight workgroups share a CU.  Which instance runs depends on H and W alone: the reduction order of a shape is fixed.
+constexpr int kPoolLdsFloats = 112 * 112 + 56 * 56 + 56 * 56 / 8;
+constexpr int kPoolLdsSmall = 4096;
+
+static inline int pool_out(int32_t n) { return (n - 1) / 2 + 1; }
+static inline int64_t pool_lds_floats(int32_t H, int32_t W) {
+  const int64_t hw = (int64_t)H * W, howo = (int64_t)pool_out(H) * pool_out(W);
+  return hw + howo + (howo + 7) / 8;
+}
+static inline bool pool_fits(int32_t H, int32_t W) { return H >= 1 && W >= 1 && pool_lds_floats(H, W) <= kPoolLdsFloats; }
+static inline bool pool_small(int32_t H, int32_t W) { return pool_lds_floats(H, W) <= kPoolLdsSmall; }
+
+// the statistics launch of clica_bn2d_act_fwd_train (bn2d.hip): partials [3][S][C] of geometry(N, HW) into `part`
+void launch_stats(hipStream_t st, const float* X, int64_t N, int32_t C, int32_t HW, float* part);
+
+#ifdef __HIPCC__
+__device__ __forceinline__ float lrelu(float z, float slope) { return z > 0.f ? z : slope * z; }
+__device__ __forceinline__ float gate(float y, float slope) { return y > 0.f ? 1.f : slope; }
+
+// VEC consecutive values; AL: one 16-byte access (the pointer is aligned), else scalar accesses of the same values
+template <int VEC, bool AL>
+__device__ __forceinline__ void load(const float* __restrict__ p, float* v) {
+  if (VEC == 4 && AL) {
+    const float4 t = *reinterpret_cast<const float4*>(p);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) v[k] = p[k];
+  }
+}
+template <int VEC, bool AL>
+__device__ __forceinline__ void store(float* __restrict__ p, const float* v) {
+  if (VEC == 4 && AL) {
+    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) p[k] = v[k];
+  }
+}
+
+// the lanes of a wave, then the waves of the workgroup in wave order: thread 0 ends with the workgroup's sums
+__device__ __forceinline__ void block_sum2(float& a, float& b, float* sh /*[kWaves * 2]*/) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { a += __shfl_down(a, off, 64); b += __shfl_down(b, off, 64); }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) { sh[2 * w] = a; sh[2 * w + 1] = b; }
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int i = 1; i < kWaves; ++i) { a += sh[2 * i]; b += sh[2 * i + 1]; }
+}
+
+__device__ __forceinline__ void sum_partials(const float* __restrict__ part, int S, int C, int c, float& s1, float& s2) {
+  const size_t plane = (size_t)S * C;
+  s1 = 0.f; s2 = 0.f;
+  for (int i = 0; i < S; ++i) {
+    s1 += part[(size_t)i * C + c];
+    s2 += part[plane + (size_t)i * C + c];
+  }
+}
+
+// The units (VEC values each, U = HW / VEC per plane) of channel c over the images n0 .. of a split form one sequence (image-major);
+// thread t takes units t, t + 256, ...  next() gives the element offset of the thread's current unit and steps on, without a division.
+struct Walk {
+  int64_t n, stride_n;      // image; C * HW
+  int q, dn, dq, U;
+  int64_t base;             // c * HW
+  __device__ Walk(int64_t n0, int U_, int C, int c, int HW) : U(U_) {
+    n = n0 + (int)threadIdx.x / U_;
+    q = (int)threadIdx.x % U_;
+    dn = kThreads / U_;
+    dq = kThreads % U_;
+    stride_n = (int64_t)C * HW;
+    base = (int64_t)c * HW;
+  }
+  template <int VEC>
+  __device__ __forceinline__ int64_t next() {
+    const int64_t off = n * stride_n + base + (int64_t)q * VEC;
+    q += dq;
+    n += dn;
+    if (q >= U) { q -= U; ++n; }
+    return off;
+  }
+};
+#endif  // __HIPCC__
+
 }  // namespace bn2d
 }  // namespace clica

@@ -19,30 +19,6 @@ using r2::Stat;
 using r2::stat_add;
 using r2::stat_merge;
 
-__device__ __forceinline__ float lrelu(float z, float slope) { return z > 0.f ? z : slope * z; }
-__device__ __forceinline__ float gate(float y, float slope) { return y > 0.f ? 1.f : slope; }
-
-// VEC consecutive values; AL: one 16-byte access (the pointer is aligned), else scalar accesses of the same values
-template <int VEC, bool AL>
-__device__ __forceinline__ void load(const float* __restrict__ p, float* v) {
-  if (VEC == 4 && AL) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) v[k] = p[k];
-  }
-}
-template <int VEC, bool AL>
-__device__ __forceinline__ void store(float* __restrict__ p, const float* v) {
-  if (VEC == 4 && AL) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) p[k] = v[k];
-  }
-}
-
 // K values (already minus the pivot) into a: their own mean and M2, then Chan's merge
 template <int K>
 __device__ __forceinline__ void stat_block(Stat& a, const float* d) {
@@ -78,16 +54,6 @@ __device__ __forceinline__ void block_merge(Stat& s, float* sh /*[kWaves * 3]*/)
     for (int i = 1; i < kWaves; ++i) stat_merge(s, Stat{sh[3 * i], sh[3 * i + 1], sh[3 * i + 2], 0.f});
 }
 
-__device__ __forceinline__ void block_sum2(float& a, float& b, float* sh /*[kWaves * 2]*/) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { a += __shfl_down(a, off, 64); b += __shfl_down(b, off, 64); }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) { sh[2 * w] = a; sh[2 * w + 1] = b; }
-  __syncthreads();
-  if (threadIdx.x == 0)
-    for (int i = 1; i < kWaves; ++i) { a += sh[2 * i]; b += sh[2 * i + 1]; }
-}
-
 // S partials of channel c in split order (every caller: the same bits)
 __device__ __forceinline__ Stat merge_partials(const float* __restrict__ part, int S, int C, int c) {
   const size_t plane = (size_t)S * C;
@@ -98,40 +64,7 @@ __device__ __forceinline__ Stat merge_partials(const float* __restrict__ part, i
   }
   return t;
 }
-__device__ __forceinline__ void sum_partials(const float* __restrict__ part, int S, int C, int c, float& s1, float& s2) {
-  const size_t plane = (size_t)S * C;
-  s1 = 0.f; s2 = 0.f;
-  for (int i = 0; i < S; ++i) {
-    s1 += part[(size_t)i * C + c];
-    s2 += part[plane + (size_t)i * C + c];
-  }
-}
-
 // ------------------------------------------------------------------------------------------------ plane geometry
-// The units (VEC values each, U = HW / VEC per plane) of channel c over the images n0 .. of a split form one sequence (image-major);
-// thread t takes units t, t + 256, ...  next() gives the element offset of the thread's current unit and steps on, without a division.
-struct Walk {
-  int64_t n, stride_n;      // image; C * HW
-  int q, dn, dq, U;
-  int64_t base;             // c * HW
-  __device__ Walk(int64_t n0, int U_, int C, int c, int HW) : U(U_) {
-    n = n0 + (int)threadIdx.x / U_;
-    q = (int)threadIdx.x % U_;
-    dn = kThreads / U_;
-    dq = kThreads % U_;
-    stride_n = (int64_t)C * HW;
-    base = (int64_t)c * HW;
-  }
-  template <int VEC>
-  __device__ __forceinline__ int64_t next() {
-    const int64_t off = n * stride_n + base + (int64_t)q * VEC;
-    q += dq;
-    n += dn;
-    if (q >= U) { q -= U; ++n; }
-    return off;
-  }
-};
-
 // grid (C, S)
 template <int VEC, bool AL>
 __global__ __launch_bounds__(kThreads) void plane_stats_k(const float* __restrict__ x, int64_t N, int C, int HW, int64_t per,
@@ -480,8 +413,6 @@ __global__ __launch_bounds__(kThreads) void small_bwd_apply_k(const float* __res
   }
 }
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // ------------------------------------------------------------------------------------------------ launches
 template <bool TRAIN>
 static void launch_apply(dim3 grid, hipStream_t st, bool small, bool quad, bool al, const float* x, const float* r, const float* gamma,
@@ -500,6 +431,22 @@ static void launch_apply(dim3 grid, hipStream_t st, bool small, bool quad, bool 
     CLICA_BN2D_APPLY((plane_apply_k<1, false, TRAIN>), HW);
   }
 #undef CLICA_BN2D_APPLY
+}
+
+// launch 1 of the training forward (also of pool2d.hip's): 16-byte loads when X allows them -- the same bits either way
+void launch_stats(hipStream_t st, const float* X, int64_t N, int32_t C, int32_t HW, float* part) {
+  const Geometry geo = geometry(N, HW);
+  const bool al = HW % 4 == 0 && aligned16(X);
+  const dim3 grid(grid_x(C, HW), (unsigned)geo.S), block(kThreads);
+  if (small_hw(HW)) {
+    if (al) hipLaunchKernelGGL(small_stats_k<true>, grid, block, 0, st, X, N, (int)C, (int)(HW / 4), geo.per, part);
+    else hipLaunchKernelGGL(small_stats_k<false>, grid, block, 0, st, X, N, (int)C, (int)(HW / 4), geo.per, part);
+  } else if (HW % 4 == 0) {
+    if (al) hipLaunchKernelGGL((plane_stats_k<4, true>), grid, block, 0, st, X, N, (int)C, (int)HW, geo.per, part);
+    else hipLaunchKernelGGL((plane_stats_k<4, false>), grid, block, 0, st, X, N, (int)C, (int)HW, geo.per, part);
+  } else {
+    hipLaunchKernelGGL((plane_stats_k<1, false>), grid, block, 0, st, X, N, (int)C, (int)HW, geo.per, part);
+  }
 }
 
 }  // namespace bn2d
@@ -536,18 +483,10 @@ extern "C" int clica_bn2d_act_fwd_train(const float* X, const float* R, const fl
   const bn2d::Geometry geo = bn2d::geometry(N, HW);
   const bool small = bn2d::small_hw(HW), quad = HW % 4 == 0;
   const bool al = quad && bn2d::aligned16(X) && bn2d::aligned16(Y) && (!R || bn2d::aligned16(R));
-  const dim3 grid(bn2d::grid_x(C, HW), (unsigned)geo.S), block(bn2d::kThreads);
+  const dim3 grid(bn2d::grid_x(C, HW), (unsigned)geo.S);
   hipStream_t st = as_stream(stream);
   float* part = static_cast<float*>(workspace);
-  if (small) {
-    if (al) hipLaunchKernelGGL(bn2d::small_stats_k<true>, grid, block, 0, st, X, N, (int)C, (int)(HW / 4), geo.per, part);
-    else hipLaunchKernelGGL(bn2d::small_stats_k<false>, grid, block, 0, st, X, N, (int)C, (int)(HW / 4), geo.per, part);
-  } else if (quad) {
-    if (al) hipLaunchKernelGGL((bn2d::plane_stats_k<4, true>), grid, block, 0, st, X, N, (int)C, (int)HW, geo.per, part);
-    else hipLaunchKernelGGL((bn2d::plane_stats_k<4, false>), grid, block, 0, st, X, N, (int)C, (int)HW, geo.per, part);
-  } else {
-    hipLaunchKernelGGL((bn2d::plane_stats_k<1, false>), grid, block, 0, st, X, N, (int)C, (int)HW, geo.per, part);
-  }
+  bn2d::launch_stats(st, X, N, C, HW, part);
   bn2d::launch_apply<true>(grid, st, small, quad, al, X, R, gamma, beta, N, (int)C, (int)HW, geo.per, (float)(N * (int64_t)HW), eps,
                            momentum, slope, part, Y, save_mean, save_invstd, running_mean, running_var);
   return launch_status("clica_bn2d_act_fwd_train");

@@ -1066,6 +1066,112 @@ def batchnorm2d_act_bwd(x, y, dy, weight, save_mean, save_invstd, slope: float =
     return dx, dr, dw, db
 
 
+# ------------------------------------------------------------------------------- the stem unit with its max-pool; global average pool
+POOL_LDS_FLOATS = 112 * 112 + 56 * 56 + 56 * 56 // 8      # csrc/bn2d.h kPoolLdsFloats: a plane, its window gradients and argmax nibbles in LDS
+AVGPOOL_MAX_HW = 1 << 14                   # csrc/pool2d.hip avgpool::kMaxHW
+_POOL_WS = {}
+
+
+def maxpool_out_hw(H: int, W: int):
+    """(Ho, Wo) of max-pool 3 / stride 2 / padding 1 in floor mode."""
+    return (int(H) - 1) // 2 + 1, (int(W) - 1) // 2 + 1
+
+
+def bn2d_maxpool_fits(H: int, W: int) -> bool:
+    """Is an H x W plane within the limit of clica_bn2d_act_maxpool_*?"""
+    Ho, Wo = maxpool_out_hw(H, W)
+    return H >= 1 and W >= 1 and H * W + Ho * Wo + (Ho * Wo + 7) // 8 <= POOL_LDS_FLOATS
+
+
+def bn2d_maxpool_workspace(N: int, C_: int, H: int, W: int, device) -> torch.Tensor:
+    """The cached workspace of clica_bn2d_act_maxpool_fwd_train / _bwd for x[N, C, H, W] on `device` (the bn2d_workspace pattern)."""
+    device = torch.device(device)
+    key = (device.index if device.index is not None else torch.cuda.current_device(), int(N), int(C_), int(H), int(W))
+    ws = _POOL_WS.get(key)
+    if ws is None:
+        nb = C.c_size_t()
+        check(load().clica_bn2d_maxpool_workspace_bytes(int(N), int(C_), int(H), int(W), C.byref(nb)), "clica_bn2d_maxpool_workspace_bytes")
+        if torch.cuda.is_current_stream_capturing():
+            raise ClicaError(f"bn2d + max-pool: no workspace for shape ({N}, {C_}, {H}, {W}) yet -- run the step once eagerly before capturing it")
+        ws = _POOL_WS[key] = torch.empty(max(nb.value, 16), dtype=torch.uint8, device=device)
+    _lib.note_graph_use(ws)
+    return ws
+
+
+def batchnorm2d_act_maxpool_fwd(x, weight, bias, running_mean=None, running_var=None, eps: float = 1e-5, momentum: float = 0.1,
+                                slope: float = 0.0):
+    """max_pool2d(leaky_relu(batch_norm(x), slope), 3, 2, 1) of contiguous NCHW x in training mode, in two launches
+    (clica_bn2d_act_maxpool_fwd_train): the activation and the pooling indices are never written.  Running statistics, when given, are
+    updated in place.  Returns (p [N, C, Ho, Wo], save_mean [C], save_invstd [C])."""
+    x = _bn2d_map("x", x)
+    N, n, H, W = x.shape
+    _norm_vec("weight", weight, n); _norm_vec("bias", bias, n)
+    if (running_mean is None) != (running_var is None):
+        raise ValueError("running_mean and running_var come together")
+    if running_mean is not None:
+        _norm_vec("running_mean", running_mean, n); _norm_vec("running_var", running_var, n)
+    ws = bn2d_maxpool_workspace(N, n, H, W, x.device)       # (validates the shape)
+    p = torch.empty((N, n) + maxpool_out_hw(H, W), dtype=torch.float32, device=x.device)
+    save_mean = torch.empty(n, dtype=torch.float32, device=x.device)
+    save_invstd = torch.empty(n, dtype=torch.float32, device=x.device)
+    check(load().clica_bn2d_act_maxpool_fwd_train(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), N, n, H, W, float(eps), float(momentum),
+                                                  float(slope), p.data_ptr(), save_mean.data_ptr(), save_invstd.data_ptr(),
+                                                  ptr(running_mean), ptr(running_var), ws.data_ptr(), ws.numel(), stream_ptr()),
+          "clica_bn2d_act_maxpool_fwd_train")
+    return p, save_mean, save_invstd
+
+
+def batchnorm2d_act_maxpool_eval(x, weight, bias, running_mean, running_var, eps: float = 1e-5, slope: float = 0.0):
+    """The same on the running statistics (inference): one launch (clica_bn2d_act_maxpool_fwd_eval)."""
+    x = _bn2d_map("x", x)
+    N, n, H, W = x.shape
+    for nm, t in (("weight", weight), ("bias", bias), ("running_mean", running_mean), ("running_var", running_var)):
+        _norm_vec(nm, t, n)
+    p = torch.empty((N, n) + maxpool_out_hw(H, W), dtype=torch.float32, device=x.device)
+    check(load().clica_bn2d_act_maxpool_fwd_eval(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), running_mean.data_ptr(),
+                                                 running_var.data_ptr(), N, n, H, W, float(eps), float(slope), p.data_ptr(), stream_ptr()),
+          "clica_bn2d_act_maxpool_fwd_eval")
+    return p
+
+
+def batchnorm2d_act_maxpool_bwd(x, dp, weight, bias, save_mean, save_invstd, slope: float = 0.0):
+    """(dx, dweight, dbias) of batchnorm2d_act_maxpool_fwd from its input x, the pooled gradient dp and the saved statistics: two
+    launches (clica_bn2d_act_maxpool_bwd); a window's gradient goes to its first maximum in scan order, as torch's does."""
+    x = _bn2d_map("x", x)
+    N, n, H, W = x.shape
+    _bn2d_map("dp", dp, (N, n) + maxpool_out_hw(H, W))
+    _norm_vec("weight", weight, n); _norm_vec("bias", bias, n)
+    _norm_vec("save_mean", save_mean, n); _norm_vec("save_invstd", save_invstd, n)
+    ws = bn2d_maxpool_workspace(N, n, H, W, x.device)
+    dx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    dw = torch.empty(n, dtype=torch.float32, device=x.device)
+    db = torch.empty(n, dtype=torch.float32, device=x.device)
+    check(load().clica_bn2d_act_maxpool_bwd(x.data_ptr(), dp.data_ptr(), weight.data_ptr(), bias.data_ptr(), save_mean.data_ptr(),
+                                            save_invstd.data_ptr(), N, n, H, W, float(slope), dx.data_ptr(), dw.data_ptr(), db.data_ptr(),
+                                            ws.data_ptr(), ws.numel(), stream_ptr()), "clica_bn2d_act_maxpool_bwd")
+    return dx, dw, db
+
+
+def avgpool2d_global_fwd(x):
+    """flatten(adaptive_avg_pool2d(x, 1), 1) of contiguous NCHW x: y [N, C], one launch (clica_avgpool2d_global_fwd)."""
+    x = _bn2d_map("x", x)
+    N, n, H, W = x.shape
+    y = torch.empty((N, n), dtype=torch.float32, device=x.device)
+    check(load().clica_avgpool2d_global_fwd(x.data_ptr(), N * n, H * W, y.data_ptr(), stream_ptr()), "clica_avgpool2d_global_fwd")
+    return y
+
+
+def avgpool2d_global_bwd(dy, H: int, W: int):
+    """dx [N, C, H, W] = dy [N, C] / (H W) on every pixel: one launch (clica_avgpool2d_global_bwd)."""
+    if dy.dim() != 2 or not dy.is_contiguous():
+        raise ValueError(f"dy must be a contiguous matrix [N, C], got shape {tuple(dy.shape)} strides {dy.stride()}")
+    require_cuda(dy, "dy")
+    N, n = dy.shape
+    dx = torch.empty((N, n, int(H), int(W)), dtype=torch.float32, device=dy.device)
+    check(load().clica_avgpool2d_global_bwd(dy.data_ptr(), N * n, int(H) * int(W), dx.data_ptr(), stream_ptr()), "clica_avgpool2d_global_bwd")
+    return dx
+
+
 def tick(counter: torch.Tensor):
     check(load().clica_tick(counter.data_ptr(), stream_ptr()), "clica_tick")
 

@@ -12,6 +12,10 @@ unit (``bn1 + relu``, ``bn2 (+ shortcut) + relu``, ``downsample[1]``) whenever `
 (NCHW) fp32 CUDA input, an affine module that tracks running statistics with a momentum, in training or in inference outside autograd.
 Anything else -- channels-last inputs among it -- runs the modules' own forward and torch's ``relu`` / ``+``.  The modules stay plain
 ``nn.BatchNorm2d`` objects that own weight, bias, running_mean, running_var and num_batches_tracked: the state dict does not change.
+
+With POOL_MODE "hip" (and NORM_MODE "hip") the two pools run on csrc/pool2d.hip as well: the stem's ``bn1 + relu + maxpool`` is one
+unit that never writes the 32 x 32 activation, pooling indices or their sparse gradient (``_stem_pool_on_hip``: a plain
+``nn.MaxPool2d(3, 2, 1)`` and a plane within the kernels' limit), and ``avgpool + flatten`` is one launch (``_avgpool_on_hip``).
 """
 from __future__ import annotations
 
@@ -29,6 +33,12 @@ __all__ = ["resnet18", "ResNet18", "BasicBlock"]
 NORM_MODE = os.environ.get("CLICA_RESNET_NORM", "hip")
 if NORM_MODE not in ("hip", "torch"):
     raise ValueError(f"CLICA_RESNET_NORM={NORM_MODE!r} (one of 'hip', 'torch')")
+
+# "hip": the stem's max-pool inside its bn2d unit and the global average pool on csrc/pool2d.hip, where NORM_MODE is "hip" and they
+# apply; "torch": nn.MaxPool2d / nn.AdaptiveAvgPool2d as before (the A/B leg).  Read at call time.
+POOL_MODE = os.environ.get("CLICA_RESNET_POOL", "hip")
+if POOL_MODE not in ("hip", "torch"):
+    raise ValueError(f"CLICA_RESNET_POOL={POOL_MODE!r} (one of 'hip', 'torch')")
 
 
 class _BN2dActFn(torch.autograd.Function):
@@ -50,6 +60,40 @@ class _BN2dActFn(torch.autograd.Function):
         dx, dr, dw, db = ops.batchnorm2d_act_bwd(x, y, gy.contiguous(), weight, save_mean, save_invstd, ctx.slope,
                                                  need_dr=ctx.needs_input_grad[1])
         return dx, dr, dw, db, None, None
+
+
+class _BN2dActPoolFn(torch.autograd.Function):
+    """The stem: nn.BatchNorm2d in training mode + ReLU + nn.MaxPool2d(3, 2, 1) on clica_bn2d_act_maxpool_fwd_train / _bwd.  The backward
+    recomputes the activation from x, so nothing of its size is saved but x itself."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, mod, slope):
+        p, save_mean, save_invstd = ops.batchnorm2d_act_maxpool_fwd(x, weight, bias, mod.running_mean, mod.running_var, mod.eps,
+                                                                    mod.momentum, slope)
+        ctx.save_for_backward(x, weight, bias, save_mean, save_invstd)
+        ctx.slope = slope
+        return p
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gp):
+        x, weight, bias, save_mean, save_invstd = ctx.saved_tensors
+        dx, dw, db = ops.batchnorm2d_act_maxpool_bwd(x, gp.contiguous(), weight, bias, save_mean, save_invstd, ctx.slope)
+        return dx, dw, db, None, None
+
+
+class _GlobalAvgPoolFn(torch.autograd.Function):
+    """flatten(nn.AdaptiveAvgPool2d(1)(x), 1) on clica_avgpool2d_global_fwd / _bwd."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.hw = (x.shape[2], x.shape[3])
+        return ops.avgpool2d_global_fwd(x)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        return ops.avgpool2d_global_bwd(gy.contiguous(), *ctx.hw)
 
 
 def _bn2d_on_hip(m, x, r=None) -> bool:
@@ -81,6 +125,36 @@ def _unit(bn, relu, x, r=None):
         bn.num_batches_tracked.add_(1)                      # in place on the device: capturable
         return _BN2dActFn.apply(x, r, bn.weight, bn.bias, bn, slope)
     return ops.batchnorm2d_act_eval(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.eps), slope, residual=r)
+
+
+def _stem_pool_on_hip(bn, pool, x) -> bool:
+    """Does the fused stem unit cover bn + relu + `pool` on this input?  Otherwise: the unfused unit, then the module."""
+    if POOL_MODE != "hip" or not _bn2d_on_hip(bn, x):
+        return False
+    one = lambda v, k: v == k or v == (k, k)
+    if not (type(pool) is nn.MaxPool2d and one(pool.kernel_size, 3) and one(pool.stride, 2) and one(pool.padding, 1) and one(pool.dilation, 1)
+            and not pool.ceil_mode and not pool.return_indices):
+        return False
+    return ops.bn2d_maxpool_fits(x.shape[2], x.shape[3])
+
+
+def _stem(bn, relu, pool, x):
+    """pool(relu(bn(x))) as one fused call where the kernels apply."""
+    if not _stem_pool_on_hip(bn, pool, x):
+        return pool(_unit(bn, relu, x))
+    if bn.training:
+        ops.bn2d_maxpool_workspace(x.shape[0], x.shape[1], x.shape[2], x.shape[3], x.device)      # (raises while capturing without a warm-up)
+        bn.num_batches_tracked.add_(1)
+        return _BN2dActPoolFn.apply(x, bn.weight, bn.bias, bn, 0.0)
+    return ops.batchnorm2d_act_maxpool_eval(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.eps), 0.0)
+
+
+def _avgpool_on_hip(pool, x) -> bool:
+    if POOL_MODE != "hip" or NORM_MODE != "hip":
+        return False
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous() and x.numel() > 0):
+        return False
+    return type(pool) is nn.AdaptiveAvgPool2d and pool.output_size in (1, (1, 1)) and x.shape[2] * x.shape[3] <= ops.AVGPOOL_MAX_HW
 
 
 class BasicBlock(nn.Module):
@@ -128,8 +202,13 @@ class ResNet18(nn.Module):
                 nn.init.constant_(m.bias, 0)
 
     def forward(self, x):
-        x = self.maxpool(self.relu(self.bn1(self.conv1(x))) if NORM_MODE != "hip" else _unit(self.bn1, self.relu, self.conv1(x)))
+        if NORM_MODE != "hip":
+            x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+        else:
+            x = _stem(self.bn1, self.relu, self.maxpool, self.conv1(x))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
+        if _avgpool_on_hip(self.avgpool, x):
+            return self.fc(_GlobalAvgPoolFn.apply(x))
         return self.fc(torch.flatten(self.avgpool(x), 1))
 
 

@@ -717,6 +717,39 @@ int clica_bn2d_act_bwd(const float* X, const float* Y, const float* dY, const fl
                        const float* save_invstd, int64_t N, int32_t C, int32_t HW, float slope, float* dX, float* dR /*or NULL*/,
                        float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, clica_stream_t stream);
 
+/* The stem unit of ResNet-18 with its max-pool (csrc/pool2d.hip): the unit above without a residual, followed by
+ * max-pool 3 x 3 / stride 2 / padding 1 in floor mode, on contiguous fp32 NCHW X[N, C, H, W]:
+ *   P[N, C, Ho, Wo] = maxpool(lrelu(gamma xhat + beta, slope)),   Ho = (H - 1) / 2 + 1,  Wo = (W - 1) / 2 + 1   (padding never wins).
+ * The activation Y, pooling indices and the sparse gradient dY are never written.  Training forward: the statistics launch of
+ * clica_bn2d_act_fwd_train (save_mean, save_invstd and the running statistics carry its bits), then one launch that forms Y per plane
+ * in LDS -- the bits of clica_bn2d_act_fwd_train's Y -- and writes the maxima.  Inference: one launch on the running statistics.
+ * Backward from X, dP, gamma, BETA (nothing saved holds Y) and the saved statistics, two launches: a window's gradient dP gate(Y)
+ * goes to its first maximum in scan order (rows, then columns of the window; torch's rule), dZ of a pixel = the sum over the windows
+ * whose first maximum it is, then dX, dgamma, dbeta as clica_bn2d_act_bwd.
+ * Limit: H W + Ho Wo + ceil(Ho Wo / 8) <= 16072 floats of LDS (a 112 x 112 plane, the stem output for 224 x 224 images, just fits); slope in [0, 1]; N H W >= 2
+ * in training.  Anything else, or a NULL pointer: CLICA_E_INVALID before any launch; a workspace smaller than
+ * clica_bn2d_maxpool_workspace_bytes (16-byte aligned, no initial contents needed, one call at a time): CLICA_E_WORKSPACE.
+ * All element offsets are 64-bit.  W % 4 == 0 with 16-byte aligned X (and dX) moves 16 bytes per lane and access; anything else takes
+ * scalar accesses and gives the same bits.  No floating-point atomics, no in-kernel counters: eager launches and graph replays give
+ * the same bits.  clica_bn2d_maxpool_workspace_bytes is host-only and validates a shape. */
+int clica_bn2d_maxpool_workspace_bytes(int64_t N, int32_t C, int32_t H, int32_t W, size_t* bytes);
+int clica_bn2d_act_maxpool_fwd_train(const float* X, const float* gamma, const float* beta, int64_t N, int32_t C, int32_t H, int32_t W,
+                                     float eps, float momentum, float slope, float* P, float* save_mean, float* save_invstd,
+                                     float* running_mean /*[C] or NULL*/, float* running_var /*[C] or NULL*/, void* workspace,
+                                     size_t workspace_bytes, clica_stream_t stream);
+int clica_bn2d_act_maxpool_fwd_eval(const float* X, const float* gamma, const float* beta, const float* running_mean,
+                                    const float* running_var, int64_t N, int32_t C, int32_t H, int32_t W, float eps, float slope, float* P,
+                                    clica_stream_t stream);
+int clica_bn2d_act_maxpool_bwd(const float* X, const float* dP, const float* gamma, const float* beta, const float* save_mean,
+                               const float* save_invstd, int64_t N, int32_t C, int32_t H, int32_t W, float slope, float* dX, float* dgamma,
+                               float* dbeta, void* workspace, size_t workspace_bytes, clica_stream_t stream);
+
+/* Global average pool over the planes of contiguous fp32 X[rows = N C, HW]: Y[r] = (sum over k of X[r, k]) x (1 / HW) in a fixed
+ * order -- the largest power of two L <= min(HW, 64) lanes own a row, lane l adds elements l, l + L, ... in turn, the lanes are added
+ * as a tree (neighbours first) -- and its backward dX[r, k] = dY[r] x (1 / HW).  One launch each.  1 <= HW <= 16384, rows <= 2^31. */
+int clica_avgpool2d_global_fwd(const float* X, int64_t rows, int32_t HW, float* Y, clica_stream_t stream);
+int clica_avgpool2d_global_bwd(const float* dY, int64_t rows, int32_t HW, float* dX, clica_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Convolution stack of the KITTI-masks encoder  --  BetaVAE_H, /root/reference/kitti_masks/model.py:41-56:
  * Conv2d(k = 4, stride 2, pad 1) + ReLU stages as implicit GEMMs (fp32 MFMA, csrc/linear.hip, conv section), channels-last.
