@@ -11,14 +11,14 @@
 //          (channel, quad) "piece" and walks over the images; a wave reads 1 KB of consecutive channels of one image, the four waves
 //          of a workgroup take images n0 + w, n0 + w + 4, ...  One workgroup = (64 pieces, image split).
 #pragma once
-#include "common.h"
-#include "r2_loss.h"      // r2::Stat / stat_add / stat_merge: Welford's update and Chan's merge
+#include "bn_core.h"      // the batch-normalisation family's shared device code; kThreads, kWaves, aligned16
 
 namespace clica {
 namespace bn2d {
 
-constexpr int kThreads = 256;                 // every kernel: 4 waves
-constexpr int kWaves = kThreads / 64;
+using bn::kThreads;                           // every kernel: 4 waves
+using bn::kWaves;
+using bn::aligned16;
 constexpr int kMaxC = 1 << 20;
 constexpr int kMaxSplits = 32;                // S: partials per channel that every apply workgroup merges again
 constexpr int64_t kPlaneSplitElems = 16384;   // plane: values of one channel a split is sized for before the cap on S (64 per thread)
@@ -50,8 +50,6 @@ static inline size_t workspace_bytes(int64_t N, int32_t C, int32_t HW) {
   return align_up((size_t)3 * (size_t)geometry(N, HW).S * (size_t)C * sizeof(float), 16);
 }
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // ------------------------------------------------------------------------------------------------ stem unit with the max-pool (pool2d.hip)
 // P = maxpool 3x3 / stride 2 / pad 1 of lrelu(gamma xhat + beta), floor mode.  The plane decomposition above: one workgroup =
 // (channel, image split); it sweeps its split's planes in batches of as many whole planes as fit kPoolLdsFloats: a batch's planes
@@ -75,9 +73,6 @@ static inline bool pool_small(int32_t H, int32_t W) { return pool_lds_floats(H, 
 void launch_stats(hipStream_t st, const float* X, int64_t N, int32_t C, int32_t HW, float* part);
 
 #ifdef __HIPCC__
-__device__ __forceinline__ float lrelu(float z, float slope) { return z > 0.f ? z : slope * z; }
-__device__ __forceinline__ float gate(float y, float slope) { return y > 0.f ? 1.f : slope; }
-
 // VEC consecutive values; AL: one 16-byte access (the pointer is aligned), else scalar accesses of the same values
 template <int VEC, bool AL>
 __device__ __forceinline__ void load(const float* __restrict__ p, float* v) {
@@ -108,15 +103,6 @@ __device__ __forceinline__ void block_sum2(float& a, float& b, float* sh /*[kWav
   __syncthreads();
   if (threadIdx.x == 0)
     for (int i = 1; i < kWaves; ++i) { a += sh[2 * i]; b += sh[2 * i + 1]; }
-}
-
-__device__ __forceinline__ void sum_partials(const float* __restrict__ part, int S, int C, int c, float& s1, float& s2) {
-  const size_t plane = (size_t)S * C;
-  s1 = 0.f; s2 = 0.f;
-  for (int i = 0; i < S; ++i) {
-    s1 += part[(size_t)i * C + c];
-    s2 += part[plane + (size_t)i * C + c];
-  }
 }
 
 // The units (VEC values each, U = HW / VEC per plane) of channel c over the images n0 .. of a split form one sequence (image-major);

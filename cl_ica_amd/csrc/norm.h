@@ -3,14 +3,13 @@
 // order, the (split | slot) partials of a workspace in index order by a LATER launch.  Phases are ordered by the stream only -- no
 // arrival counter, no atomics --, so eager launches and graph replays give the same bits.
 #pragma once
-#include "common.h"
-#include "r2_loss.h"      // r2::Stat / stat_add / stat_merge: Welford's update and Chan's merge
+#include "bn_core.h"      // the batch-normalisation family's shared device code; kThreads, kWaves
 
 namespace clica {
 namespace norm {
 
-constexpr int kThreads = 256;                 // every kernel: 4 waves
-constexpr int kWaves = kThreads / 64;
+using bn::kThreads;                           // every kernel: 4 waves
+using bn::kWaves;
 constexpr int kMaxC = 1 << 20;
 
 // ---- BatchNorm: columns across the lanes of a wave, 64 per workgroup; rows across waves, workgroups (row tiles) and row splits

@@ -7,7 +7,8 @@
 // as pivot, as r2_loss.hip) per (row split, column); bn_apply_k -- the next launch on the stream -- merges the S partials of its 64
 // columns in split order in EVERY workgroup (the same bits everywhere, no hand-off between workgroups), normalises its row tile, and
 // row tile 0 writes save_mean / save_invstd and the running statistics.  The backward is the same pair: bn_bwd_sums_k (sum dz,
-// sum dz xhat per split), bn_bwd_apply_k.  Inference: bn_eval_k, one element-wise launch.
+// sum dz xhat per split), bn_bwd_apply_k.  Inference: bn_apply_k<false> on the running statistics, one element-wise launch.
+// The channel finish, the element functions and the merges are bn_core.h's, shared with bn2d.hip and pool2d.hip.
 // GroupNorm(1, C) (row statistics): gn_fwd_k, one wave per row, true two-pass (mean, then sum (x - mean)^2), the row in registers up
 // to 1024 columns; gn_bwd_k the same layout, each lane keeping d gamma / d beta partials of its own columns over the rows of its
 // wave slot; gn_param_reduce_k sums the slots in slot order.
@@ -19,10 +20,9 @@ namespace norm {
 
 using r2::Stat;
 using r2::stat_add;
-using r2::stat_merge;
+using bn::lrelu;
+using bn::gate;
 
-__device__ __forceinline__ float lrelu(float z, float slope) { return z > 0.f ? z : slope * z; }
-__device__ __forceinline__ float gate(float y, float slope) { return y > 0.f ? 1.f : slope; }
 __device__ __forceinline__ float wave_sum(float v) {       // butterfly: every lane ends with the same bits
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -33,7 +33,7 @@ __device__ __forceinline__ float wave_sum(float v) {       // butterfly: every l
 // grid (64-column chunks, S row splits).  Lane = column (256 contiguous bytes per row and wave), wave w takes rows r0 + w, r0 + w + 4, ...
 __global__ __launch_bounds__(kThreads) void bn_stats_k(const float* __restrict__ x, int64_t M, int C, int64_t split_rows,
                                                       float* __restrict__ part) {
-  __shared__ float sh[(kWaves - 1) * 3 * 64];
+  __shared__ float sh[bn::kColumnStatLds];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int col = (int)blockIdx.x * 64 + lane;
   const int split = (int)blockIdx.y, S = (int)gridDim.y;
@@ -49,23 +49,17 @@ __global__ __launch_bounds__(kThreads) void bn_stats_k(const float* __restrict__
     }
     for (; r < r1; r += kWaves) stat_add(s, x[r * C + col] - pivot, 0.f);
   }
-  if (w > 0) {
-    float* p = sh + (w - 1) * 3 * 64 + lane;
-    p[0] = s.cnt; p[64] = s.mean; p[128] = s.m2;
-  }
-  __syncthreads();
+  bn::column_merge(s, sh, col < C);
   if (w == 0 && col < C) {
-    for (int i = 0; i < kWaves - 1; ++i) {               // the workgroup's waves in wave order
-      const float* p = sh + i * 3 * 64 + lane;
-      stat_merge(s, Stat{p[0], p[64], p[128], 0.f});
-    }
     const size_t plane = (size_t)S * C;
     float* q = part + (size_t)split * C + col;
     q[0] = s.cnt; q[plane] = s.mean; q[2 * plane] = s.m2;
   }
 }
 
-// grid (row tiles, 64-column chunks).  No barrier: a lane beyond C leaves at once.
+// grid (row tiles, 64-column chunks).  TRAIN: batch statistics from the partials, row tile 0 is the writer; otherwise the running
+// statistics (inference).  No barrier: a lane beyond C leaves at once.
+template <bool TRAIN>
 __global__ __launch_bounds__(kThreads) void bn_apply_k(const float* __restrict__ x, const float* __restrict__ gamma,
                                                       const float* __restrict__ beta, int64_t M, int C, int S, float Mf, float eps,
                                                       float momentum, float slope, const float* __restrict__ part, float* __restrict__ y,
@@ -74,53 +68,14 @@ __global__ __launch_bounds__(kThreads) void bn_apply_k(const float* __restrict__
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int col = (int)blockIdx.y * 64 + lane;
   if (col >= C) return;
-  const size_t plane = (size_t)S * C;
-  Stat t{0.f, 0.f, 0.f, 0.f};
-  for (int i0 = 0; i0 < S; i0 += 8) {                     // split order: the same bits in every workgroup of this column chunk
-    float cnt[8], mu[8], m2[8];                           // (eight partials' loads in flight; an empty one merges as nothing)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float* p = part + (size_t)(i0 + j) * C + col;
-      const bool in = i0 + j < S;
-      cnt[j] = in ? p[0] : 0.f; mu[j] = in ? p[plane] : 0.f; m2[j] = in ? p[2 * plane] : 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) stat_merge(t, Stat{cnt[j], mu[j], m2[j], 0.f});
-  }
-  const float mean = x[col] + t.mean;
-  const float invstd = 1.f / sqrtf(t.m2 / Mf + eps);
-  if (blockIdx.x == 0 && w == 0) {
-    save_mean[col] = mean;
-    save_invstd[col] = invstd;
-    if (running_mean) running_mean[col] = (1.f - momentum) * running_mean[col] + momentum * mean;
-    if (running_var) running_var[col] = (1.f - momentum) * running_var[col] + momentum * (t.m2 / (Mf - 1.f));      // unbiased
-  }
+  const bn::Norm nm = TRAIN ? bn::finish_train(bn::merge_stats(part, S, C, col), x[col], Mf, eps, momentum, col, blockIdx.x == 0 && w == 0,
+                                               save_mean, save_invstd, running_mean, running_var)
+                            : bn::finish_eval(running_mean, running_var, col, eps);
   const float g = gamma[col], b = beta[col];
   const int64_t row0 = (int64_t)blockIdx.x * kBnTileRows;
   const int64_t row1 = row0 + kBnTileRows < M ? row0 + kBnTileRows : M;
 #pragma unroll 4
-  for (int64_t r = row0 + w; r < row1; r += kWaves) {
-    const float xh = (x[r * C + col] - mean) * invstd;
-    y[r * C + col] = lrelu(fmaf(g, xh, b), slope);
-  }
-}
-
-__global__ __launch_bounds__(kThreads) void bn_eval_k(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                     const float* __restrict__ beta, const float* __restrict__ running_mean,
-                                                     const float* __restrict__ running_var, int64_t M, int C, float eps, float slope,
-                                                     float* __restrict__ y) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int col = (int)blockIdx.y * 64 + lane;
-  if (col >= C) return;
-  const float mean = running_mean[col], invstd = 1.f / sqrtf(running_var[col] + eps);
-  const float g = gamma[col], b = beta[col];
-  const int64_t row0 = (int64_t)blockIdx.x * kBnTileRows;
-  const int64_t row1 = row0 + kBnTileRows < M ? row0 + kBnTileRows : M;
-#pragma unroll 4
-  for (int64_t r = row0 + w; r < row1; r += kWaves) {
-    const float xh = (x[r * C + col] - mean) * invstd;
-    y[r * C + col] = lrelu(fmaf(g, xh, b), slope);
-  }
+  for (int64_t r = row0 + w; r < row1; r += kWaves) y[r * C + col] = bn::fwd(x[r * C + col], nm, g, b, slope);
 }
 
 // the geometry of bn_stats_k: sum dz and sum dz xhat per (split, column), dz = dy gate(y), xhat = (x - save_mean) save_invstd
@@ -128,7 +83,7 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_sums_k(const float* __restric
                                                          const float* __restrict__ dy, const float* __restrict__ save_mean,
                                                          const float* __restrict__ save_invstd, int64_t M, int C, int64_t split_rows,
                                                          float slope, float* __restrict__ part) {
-  __shared__ float sh[(kWaves - 1) * 2 * 64];
+  __shared__ float sh[bn::kColumnSumsLds];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int col = (int)blockIdx.x * 64 + lane;
   const int split = (int)blockIdx.y, S = (int)gridDim.y;
@@ -136,26 +91,15 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_sums_k(const float* __restric
   const int64_t r1 = r0 + split_rows < M ? r0 + split_rows : M;
   float s1 = 0.f, s2 = 0.f;
   if (col < C) {
-    const float mean = save_mean[col], invstd = save_invstd[col];
+    const bn::Norm nm{save_mean[col], save_invstd[col]};
 #pragma unroll 4
     for (int64_t r = r0 + w; r < r1; r += kWaves) {
       const int64_t e = r * C + col;
-      const float dz = dy[e] * gate(y[e], slope);
-      const float xh = (x[e] - mean) * invstd;
-      s1 += dz;
-      s2 = fmaf(dz, xh, s2);
+      bn::bwd_sums(s1, s2, bn::bwd_dz(dy[e], y[e], slope), bn::xhat(x[e], nm));
     }
   }
-  if (w > 0) {
-    float* p = sh + (w - 1) * 2 * 64 + lane;
-    p[0] = s1; p[64] = s2;
-  }
-  __syncthreads();
+  bn::column_sums(s1, s2, sh, col < C);
   if (w == 0 && col < C) {
-    for (int i = 0; i < kWaves - 1; ++i) {
-      const float* p = sh + i * 2 * 64 + lane;
-      s1 += p[0]; s2 += p[64];
-    }
     float* q = part + (size_t)split * C + col;
     q[0] = s1; q[(size_t)S * C] = s2;
   }
@@ -169,33 +113,21 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_apply_k(const float* __restri
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int col = (int)blockIdx.y * 64 + lane;
   if (col >= C) return;
-  const size_t plane = (size_t)S * C;
-  float s1 = 0.f, s2 = 0.f;
-  for (int i0 = 0; i0 < S; i0 += 8) {                     // split order, eight partials' loads in flight
-    float a[8], b[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float* p = part + (size_t)(i0 + j) * C + col;
-      const bool in = i0 + j < S;
-      a[j] = in ? p[0] : 0.f; b[j] = in ? p[plane] : 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { s1 += a[j]; s2 += b[j]; }
-  }
+  float s1, s2;
+  bn::merge_sums(part, S, C, col, s1, s2);
   if (blockIdx.x == 0 && w == 0) {
     dgamma[col] = s2;
     dbeta[col] = s1;
   }
-  const float mean = save_mean[col], invstd = save_invstd[col];
-  const float k = gamma[col] * invstd, m1 = s1 / Mf, m2 = s2 / Mf;
+  const bn::Norm nm{save_mean[col], save_invstd[col]};
+  const bn::Bwd bw = bn::bwd_coeffs(gamma[col], nm.invstd, s1, s2, Mf);
   const int64_t row0 = (int64_t)blockIdx.x * kBnTileRows;
   const int64_t row1 = row0 + kBnTileRows < M ? row0 + kBnTileRows : M;
 #pragma unroll 4
   for (int64_t r = row0 + w; r < row1; r += kWaves) {
     const int64_t e = r * C + col;
-    const float dz = dy[e] * gate(y[e], slope);
-    const float xh = (x[e] - mean) * invstd;
-    dx[e] = k * (dz - m1 - xh * m2);
+    const float dz = bn::bwd_dz(dy[e], y[e], slope);
+    dx[e] = bn::bwd_dx(dz, bn::xhat(x[e], nm), bw);
   }
 }
 
@@ -343,8 +275,6 @@ __global__ __launch_bounds__(kThreads) void gn_param_reduce_k(const float* __res
   dbeta[c] = sb;
 }
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace norm
 }  // namespace clica
 
@@ -368,15 +298,12 @@ extern "C" int clica_bn_lrelu_fwd_train(const float* X, const float* gamma, cons
                                         float* running_var, void* workspace, size_t workspace_bytes, clica_stream_t stream) {
   CLICA_NORM_SHAPE("clica_bn_lrelu_fwd_train", 2);
   CLICA_CHECK_ARG(X && gamma && beta && Y && save_mean && save_invstd && workspace, "clica_bn_lrelu_fwd_train: NULL pointer");
-  CLICA_CHECK_ARG(norm::aligned16(workspace), "clica_bn_lrelu_fwd_train: workspace must be 16-byte aligned");
-  const size_t need = norm::bn_workspace_bytes(M, C);
-  CLICA_CHECK_ARG(workspace_bytes >= need, "clica_bn_lrelu_fwd_train: workspace of %zu bytes, %zu needed (clica_norm_workspace_bytes)",
-                  workspace_bytes, need);
+  CLICA_BN_WORKSPACE("clica_bn_lrelu_fwd_train", norm::bn_workspace_bytes(M, C), "clica_norm_workspace_bytes", CLICA_E_INVALID);
   const int S = norm::bn_splits(M), chunks = norm::bn_chunks(C);
   float* part = static_cast<float*>(workspace);
   hipLaunchKernelGGL(norm::bn_stats_k, dim3((unsigned)chunks, (unsigned)S), dim3(norm::kThreads), 0, as_stream(stream), X, M, (int)C,
                      norm::bn_split_rows(M), part);
-  hipLaunchKernelGGL(norm::bn_apply_k, dim3((unsigned)norm::bn_tiles(M), (unsigned)chunks), dim3(norm::kThreads), 0, as_stream(stream), X,
+  hipLaunchKernelGGL(norm::bn_apply_k<true>, dim3((unsigned)norm::bn_tiles(M), (unsigned)chunks), dim3(norm::kThreads), 0, as_stream(stream), X,
                      gamma, beta, M, (int)C, S, (float)M, eps, momentum, slope, part, Y, save_mean, save_invstd, running_mean, running_var);
   return launch_status("clica_bn_lrelu_fwd_train");
 }
@@ -386,8 +313,10 @@ extern "C" int clica_bn_lrelu_fwd_eval(const float* X, const float* gamma, const
                                        clica_stream_t stream) {
   CLICA_NORM_SHAPE("clica_bn_lrelu_fwd_eval", 1);
   CLICA_CHECK_ARG(X && gamma && beta && running_mean && running_var && Y, "clica_bn_lrelu_fwd_eval: NULL pointer");
-  hipLaunchKernelGGL(norm::bn_eval_k, dim3((unsigned)norm::bn_tiles(M), (unsigned)norm::bn_chunks(C)), dim3(norm::kThreads), 0,
-                     as_stream(stream), X, gamma, beta, running_mean, running_var, M, (int)C, eps, slope, Y);
+  // (the inference instance only reads the running statistics)
+  hipLaunchKernelGGL(norm::bn_apply_k<false>, dim3((unsigned)norm::bn_tiles(M), (unsigned)norm::bn_chunks(C)), dim3(norm::kThreads), 0,
+                     as_stream(stream), X, gamma, beta, M, (int)C, 0, 0.f, eps, 0.f, slope, nullptr, Y, nullptr, nullptr,
+                     const_cast<float*>(running_mean), const_cast<float*>(running_var));
   return launch_status("clica_bn_lrelu_fwd_eval");
 }
 
@@ -396,10 +325,7 @@ extern "C" int clica_bn_lrelu_bwd(const float* X, const float* Y, const float* d
                                   void* workspace, size_t workspace_bytes, clica_stream_t stream) {
   CLICA_NORM_SHAPE("clica_bn_lrelu_bwd", 2);
   CLICA_CHECK_ARG(X && Y && dY && gamma && save_mean && save_invstd && dX && dgamma && dbeta && workspace, "clica_bn_lrelu_bwd: NULL pointer");
-  CLICA_CHECK_ARG(norm::aligned16(workspace), "clica_bn_lrelu_bwd: workspace must be 16-byte aligned");
-  const size_t need = norm::bn_workspace_bytes(M, C);
-  CLICA_CHECK_ARG(workspace_bytes >= need, "clica_bn_lrelu_bwd: workspace of %zu bytes, %zu needed (clica_norm_workspace_bytes)",
-                  workspace_bytes, need);
+  CLICA_BN_WORKSPACE("clica_bn_lrelu_bwd", norm::bn_workspace_bytes(M, C), "clica_norm_workspace_bytes", CLICA_E_INVALID);
   const int S = norm::bn_splits(M), chunks = norm::bn_chunks(C);
   float* part = static_cast<float*>(workspace);
   hipLaunchKernelGGL(norm::bn_bwd_sums_k, dim3((unsigned)chunks, (unsigned)S), dim3(norm::kThreads), 0, as_stream(stream), X, Y, dY,
@@ -426,10 +352,7 @@ extern "C" int clica_gn_lrelu_bwd(const float* X, const float* Y, const float* d
                                   size_t workspace_bytes, clica_stream_t stream) {
   CLICA_NORM_SHAPE("clica_gn_lrelu_bwd", 1);
   CLICA_CHECK_ARG(X && Y && dY && gamma && mean && rstd && dX && dgamma && dbeta && workspace, "clica_gn_lrelu_bwd: NULL pointer");
-  CLICA_CHECK_ARG(norm::aligned16(workspace), "clica_gn_lrelu_bwd: workspace must be 16-byte aligned");
-  const size_t need = norm::gn_workspace_bytes(M, C);
-  CLICA_CHECK_ARG(workspace_bytes >= need, "clica_gn_lrelu_bwd: workspace of %zu bytes, %zu needed (clica_norm_workspace_bytes)",
-                  workspace_bytes, need);
+  CLICA_BN_WORKSPACE("clica_gn_lrelu_bwd", norm::gn_workspace_bytes(M, C), "clica_norm_workspace_bytes", CLICA_E_INVALID);
   const dim3 grid((unsigned)norm::gn_bwd_blocks(M)), block(norm::kThreads);
   float* part = static_cast<float*>(workspace);
   if (C <= norm::kGnRegCols)

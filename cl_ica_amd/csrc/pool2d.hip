@@ -4,9 +4,9 @@
 //      y = lrelu(gamma xhat + beta, slope),   P[n, c, ho, wo] = max of y over rows 2 ho - 1 .. 2 ho + 1, columns 2 wo - 1 .. 2 wo + 1
 //    (the part inside the plane: padding never wins).  y, pooling indices and the sparse gradient dy never reach memory.
 //    Training forward: bn2d.hip's statistics launch (the same partials, hence the bits of the unfused unit in save_mean, save_invstd
-//    and the running statistics), then pool_fwd_k: every workgroup merges the partials of its channel (loads issued eight ahead of the
-//    merges, split order), forms y for a batch of whole planes in LDS with the expression of plane_apply_k -- the same bits -- and
-//    writes the maxima.  Inference: pool_fwd_k<.., false> on the running statistics, one launch.
+//    and the running statistics), then pool_fwd_k: every workgroup merges the partials of its channel (bn_core.h's merge and channel
+//    finish, as bn2d.hip's apply_k), forms y for a batch of whole planes in LDS with bn_core.h's forward element function -- the
+//    unfused unit's, hence the same bits -- and writes the maxima.  Inference: pool_fwd_k<.., false> on the running statistics, one launch.
 //    Backward from x, dP, gamma, beta and the saved statistics: a batch's xhat planes go to LDS; a thread per window forms y from xhat,
 //    finds the window's FIRST maximum in scan order (rows, then columns: torch's rule) and leaves its position (a nibble) and
 //    dP gate(y) in LDS; then a pixel GATHERS  dz = the sum over the <= 4 windows that contain it and whose first maximum it is.
@@ -21,27 +21,6 @@
 
 namespace clica {
 namespace bn2d {
-
-using r2::Stat;
-using r2::stat_merge;
-
-// merge_partials of bn2d.hip with the loads of eight partials in flight before their merges: split order, the same bits
-__device__ __forceinline__ Stat merge_partials_ahead(const float* __restrict__ part, int S, int C, int c) {
-  const size_t plane = (size_t)S * C;
-  Stat t{0.f, 0.f, 0.f, 0.f};
-  for (int i0 = 0; i0 < S; i0 += 8) {
-    float a[8], m[8], q[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float* p = part + (size_t)(i0 + j < S ? i0 + j : S - 1) * C + c;
-      a[j] = p[0]; m[j] = p[plane]; q[j] = p[2 * plane];
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (i0 + j < S) stat_merge(t, Stat{a[j], m[j], q[j], 0.f});
-  }
-  return t;
-}
 
 template <int VEC>
 __device__ __forceinline__ void lds_store(float* p, const float* v) {
@@ -69,7 +48,7 @@ __device__ __forceinline__ float window_max(const float* pl, int ho, int wo, int
       const int ww = 2 * wo - 1 + dx;
       const bool vc = ww >= 0 && ww < W;
       float v = pl[(vr ? hh : 2 * ho) * W + (vc ? ww : 2 * wo)];      // (the centre is always inside)
-      if (XHAT) v = lrelu(fmaf(g, v, b), slope);
+      if (XHAT) v = bn::fwd_xhat(v, g, b, slope);
       if (vr && vc && v > m) { m = v; code = dy * 3 + dx; }
     }
   }
@@ -86,21 +65,9 @@ __global__ __launch_bounds__(kThreads) void pool_fwd_k(const float* __restrict__
   __shared__ __attribute__((aligned(16))) float sy[LDSF];
   const int c = (int)blockIdx.x, split = (int)blockIdx.y, S = (int)gridDim.y;
   const int HW = H * W, Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, HoWo = Ho * Wo;
-  float mean, invstd;
-  if (TRAIN) {
-    const Stat t = merge_partials_ahead(part, S, C, c);
-    mean = x[(int64_t)c * HW] + t.mean;
-    invstd = 1.f / sqrtf(t.m2 / Mf + eps);
-    if (split == 0 && threadIdx.x == 0) {
-      save_mean[c] = mean;
-      save_invstd[c] = invstd;
-      if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean;
-      if (running_var) running_var[c] = (1.f - momentum) * running_var[c] + momentum * (t.m2 / (Mf - 1.f));      // unbiased
-    }
-  } else {
-    mean = running_mean[c];
-    invstd = 1.f / sqrtf(running_var[c] + eps);
-  }
+  const bn::Norm nm = TRAIN ? bn::finish_train(bn::merge_stats(part, S, C, c), x[(int64_t)c * HW], Mf, eps, momentum, c,
+                                               split == 0 && threadIdx.x == 0, save_mean, save_invstd, running_mean, running_var)
+                            : bn::finish_eval(running_mean, running_var, c, eps);
   const float g = gamma[c], b = beta[c];
   const int64_t n0 = (int64_t)split * per;
   const int64_t n1 = n0 + per < N ? n0 + per : N;
@@ -115,7 +82,7 @@ __global__ __launch_bounds__(kThreads) void pool_fwd_k(const float* __restrict__
       float v[VEC];
       load<VEC, AL>(x + wk.next<VEC>(), v);
 #pragma unroll
-      for (int k = 0; k < VEC; ++k) v[k] = lrelu(fmaf(g, (v[k] - mean) * invstd, b), slope);
+      for (int k = 0; k < VEC; ++k) v[k] = bn::fwd(v[k], nm, g, b, slope);
       lds_store<VEC>(sy + i * VEC, v);
     }
     __syncthreads();
@@ -132,8 +99,8 @@ __global__ __launch_bounds__(kThreads) void pool_fwd_k(const float* __restrict__
 
 // a batch's xhat planes to sl[0 .. cnt HW)
 template <int VEC, bool AL>
-__device__ __forceinline__ void pool_bwd_stage(float* sl, const float* __restrict__ x, int64_t nb, int cnt, int C, int c, int HW, float mean,
-                                               float invstd) {
+__device__ __forceinline__ void pool_bwd_stage(float* sl, const float* __restrict__ x, int64_t nb, int cnt, int C, int c, int HW,
+                                               const bn::Norm& nm) {
   const int U = HW / VEC, T = cnt * U;
   Walk wk(nb, U, C, c, HW);
 #pragma unroll 4
@@ -141,7 +108,7 @@ __device__ __forceinline__ void pool_bwd_stage(float* sl, const float* __restric
     float v[VEC];
     load<VEC, AL>(x + wk.next<VEC>(), v);
 #pragma unroll
-    for (int k = 0; k < VEC; ++k) v[k] = (v[k] - mean) * invstd;
+    for (int k = 0; k < VEC; ++k) v[k] = bn::xhat(v[k], nm);
     lds_store<VEC>(sl + i * VEC, v);
   }
 }
@@ -161,7 +128,7 @@ __device__ __forceinline__ void pool_bwd_windows(const float* sl, float* sd, uns
         const float d = dP[((nb + gi) * C + c) * HoWo + r];
         int code;
         const float m = window_max<true>(sl + gi * HW, ho, wo, H, W, g, b, slope, code);
-        sd[o] = d * gate(m, slope);
+        sd[o] = bn::bwd_dz(d, m, slope);
         byte |= (unsigned)code << (4 * j);
       }
     }
@@ -196,7 +163,8 @@ __global__ __launch_bounds__(kThreads) void pool_sums_k(const float* __restrict_
   __shared__ float sh[kWaves * 2];
   const int c = (int)blockIdx.x, split = (int)blockIdx.y, S = (int)gridDim.y;
   const int HW = H * W, Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, HoWo = Ho * Wo;
-  const float mean = save_mean[c], invstd = save_invstd[c], g = gamma[c], b = beta[c];
+  const bn::Norm nm{save_mean[c], save_invstd[c]};
+  const float g = gamma[c], b = beta[c];
   const int64_t n0 = (int64_t)split * per;
   const int64_t n1 = n0 + per < N ? n0 + per : N;
   const int G = LDSF / (HW + HoWo + (HoWo + 7) / 8);
@@ -206,7 +174,7 @@ __global__ __launch_bounds__(kThreads) void pool_sums_k(const float* __restrict_
     const int cnt = n1 - nb < G ? (int)(n1 - nb) : G;
     float* sd = sl + cnt * HW;
     unsigned char* sc = reinterpret_cast<unsigned char*>(sd + cnt * HoWo);
-    pool_bwd_stage<VEC, AL>(sl, x, nb, cnt, C, c, HW, mean, invstd);
+    pool_bwd_stage<VEC, AL>(sl, x, nb, cnt, C, c, HW, nm);
     __syncthreads();
     pool_bwd_windows(sl, sd, sc, dP, nb, cnt, C, c, H, W, Ho, Wo, g, b, slope);
     __syncthreads();
@@ -215,9 +183,7 @@ __global__ __launch_bounds__(kThreads) void pool_sums_k(const float* __restrict_
       const int gi = i / U, rem = (i - gi * U) * VEC, h = rem / W, w = rem - h * W;
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
-        const float dz = pool_dz(sd, sc, gi * HoWo, h, w + k, Ho, Wo);
-        s1 += dz;
-        s2 = fmaf(dz, sl[i * VEC + k], s2);
+        bn::bwd_sums(s1, s2, pool_dz(sd, sc, gi * HoWo, h, w + k, Ho, Wo), sl[i * VEC + k]);
       }
     }
     __syncthreads();
@@ -241,13 +207,14 @@ __global__ __launch_bounds__(kThreads) void pool_bwd_apply_k(const float* __rest
   const int c = (int)blockIdx.x, split = (int)blockIdx.y, S = (int)gridDim.y;
   const int HW = H * W, Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, HoWo = Ho * Wo;
   float s1, s2;
-  sum_partials(part, S, C, c, s1, s2);
+  bn::merge_sums(part, S, C, c, s1, s2);
   if (split == 0 && threadIdx.x == 0) {
     dgamma[c] = s2;
     dbeta[c] = s1;
   }
-  const float mean = save_mean[c], invstd = save_invstd[c], g = gamma[c], b = beta[c];
-  const float kk = g * invstd, m1 = s1 / Mf, m2 = s2 / Mf;
+  const bn::Norm nm{save_mean[c], save_invstd[c]};
+  const float g = gamma[c], b = beta[c];
+  const bn::Bwd bw = bn::bwd_coeffs(g, nm.invstd, s1, s2, Mf);
   const int64_t n0 = (int64_t)split * per;
   const int64_t n1 = n0 + per < N ? n0 + per : N;
   const int G = LDSF / (HW + HoWo + (HoWo + 7) / 8);
@@ -256,7 +223,7 @@ __global__ __launch_bounds__(kThreads) void pool_bwd_apply_k(const float* __rest
     const int cnt = n1 - nb < G ? (int)(n1 - nb) : G;
     float* sd = sl + cnt * HW;
     unsigned char* sc = reinterpret_cast<unsigned char*>(sd + cnt * HoWo);
-    pool_bwd_stage<VEC, AL>(sl, x, nb, cnt, C, c, HW, mean, invstd);
+    pool_bwd_stage<VEC, AL>(sl, x, nb, cnt, C, c, HW, nm);
     __syncthreads();
     pool_bwd_windows(sl, sd, sc, dP, nb, cnt, C, c, H, W, Ho, Wo, g, b, slope);
     __syncthreads();
@@ -265,13 +232,28 @@ __global__ __launch_bounds__(kThreads) void pool_bwd_apply_k(const float* __rest
       const int gi = i / U, rem = (i - gi * U) * VEC, h = rem / W, w = rem - h * W;
       float v[VEC];
 #pragma unroll
-      for (int k = 0; k < VEC; ++k) {
-        const float dz = pool_dz(sd, sc, gi * HoWo, h, w + k, Ho, Wo);
-        v[k] = kk * (dz - m1 - sl[i * VEC + k] * m2);
-      }
+      for (int k = 0; k < VEC; ++k) v[k] = bn::bwd_dx(pool_dz(sd, sc, gi * HoWo, h, w + k, Ho, Wo), sl[i * VEC + k], bw);
       store<VEC, AL>(dx + ((nb + gi) * C + c) * HW + rem, v);
     }
     __syncthreads();
+  }
+}
+
+// f(instance): the LDS size from H and W, quads from W alone (the reduction order); `al` only picks 16-byte accesses
+template <int LDSF_, int VEC_, bool AL_>
+struct PoolInstance { static constexpr int LDSF = LDSF_, VEC = VEC_; static constexpr bool AL = AL_; };
+
+template <class F>
+static void with_pool_instance(int H, int W, bool al, F&& f) {
+  const bool quad = W % 4 == 0;
+  if (pool_small(H, W)) {
+    if (!quad) f(PoolInstance<kPoolLdsSmall, 1, false>{});
+    else if (al) f(PoolInstance<kPoolLdsSmall, 4, true>{});
+    else f(PoolInstance<kPoolLdsSmall, 4, false>{});
+  } else {
+    if (!quad) f(PoolInstance<kPoolLdsFloats, 1, false>{});
+    else if (al) f(PoolInstance<kPoolLdsFloats, 4, true>{});
+    else f(PoolInstance<kPoolLdsFloats, 4, false>{});
   }
 }
 
@@ -282,19 +264,10 @@ static void launch_pool_fwd(hipStream_t st, const float* x, const float* gamma, 
   const Geometry geo = geometry(N, H * W);
   const dim3 grid((unsigned)C, (unsigned)geo.S), block(kThreads);
   const float Mf = (float)(N * (int64_t)H * W);
-#define CLICA_POOL_FWD(K) \
-  hipLaunchKernelGGL(K, grid, block, 0, st, x, gamma, beta, N, C, H, W, geo.per, Mf, eps, momentum, slope, part, P, save_mean, save_invstd, rm, rv)
-  const bool small = pool_small(H, W), quad = W % 4 == 0, al = quad && aligned16(x);
-  if (small) {
-    if (!quad) CLICA_POOL_FWD((pool_fwd_k<kPoolLdsSmall, 1, false, TRAIN>));
-    else if (al) CLICA_POOL_FWD((pool_fwd_k<kPoolLdsSmall, 4, true, TRAIN>));
-    else CLICA_POOL_FWD((pool_fwd_k<kPoolLdsSmall, 4, false, TRAIN>));
-  } else {
-    if (!quad) CLICA_POOL_FWD((pool_fwd_k<kPoolLdsFloats, 1, false, TRAIN>));
-    else if (al) CLICA_POOL_FWD((pool_fwd_k<kPoolLdsFloats, 4, true, TRAIN>));
-    else CLICA_POOL_FWD((pool_fwd_k<kPoolLdsFloats, 4, false, TRAIN>));
-  }
-#undef CLICA_POOL_FWD
+  with_pool_instance(H, W, W % 4 == 0 && aligned16(x), [&](auto i) {
+    hipLaunchKernelGGL((pool_fwd_k<i.LDSF, i.VEC, i.AL, TRAIN>), grid, block, 0, st, x, gamma, beta, N, C, H, W, geo.per, Mf, eps, momentum, slope,
+                       part, P, save_mean, save_invstd, rm, rv);
+  });
 }
 
 }  // namespace bn2d
@@ -352,15 +325,8 @@ using namespace clica;
 #define CLICA_POOL_SLOPE(fn) \
   CLICA_CHECK_ARG(slope >= 0.f && slope <= 1.f, fn ": slope=%g must be in [0, 1] (the pool's argmax is taken after the activation)", slope)
 
-#define CLICA_POOL_WORKSPACE(fn)                                                                                          \
-  do {                                                                                                                    \
-    CLICA_CHECK_ARG(bn2d::aligned16(workspace), fn ": workspace must be 16-byte aligned");                                \
-    const size_t need = bn2d::workspace_bytes(N, C, H * W);                                                               \
-    if (workspace_bytes < need) {                                                                                         \
-      set_error(fn ": workspace of %zu bytes, %zu needed (clica_bn2d_maxpool_workspace_bytes)", workspace_bytes, need);   \
-      return CLICA_E_WORKSPACE;                                                                                           \
-    }                                                                                                                     \
-  } while (0)
+#define CLICA_POOL_WORKSPACE(fn) \
+  CLICA_BN_WORKSPACE(fn, bn2d::workspace_bytes(N, C, H * W), "clica_bn2d_maxpool_workspace_bytes", CLICA_E_WORKSPACE)
 
 extern "C" int clica_bn2d_maxpool_workspace_bytes(int64_t N, int32_t C, int32_t H, int32_t W, size_t* bytes) {
   CLICA_CHECK_ARG(bytes != nullptr, "clica_bn2d_maxpool_workspace_bytes: bytes is NULL");
@@ -410,24 +376,12 @@ extern "C" int clica_bn2d_act_maxpool_bwd(const float* X, const float* dP, const
   hipStream_t st = as_stream(stream);
   float* part = static_cast<float*>(workspace);
   const float Mf = (float)(N * (int64_t)H * W);
-#define CLICA_POOL_BWD(F, V, A)                                                                                                             \
-  do {                                                                                                                                    \
-    hipLaunchKernelGGL((bn2d::pool_sums_k<F, V, A>), grid, block, 0, st, X, dP, gamma, beta, save_mean, save_invstd, N, (int)C, (int)H,      \
-                       (int)W, geo.per, slope, part);                                                                                     \
-    hipLaunchKernelGGL((bn2d::pool_bwd_apply_k<F, V, A>), grid, block, 0, st, X, dP, gamma, beta, save_mean, save_invstd, N, (int)C, (int)H, \
-                       (int)W, geo.per, Mf, slope, part, dX, dgamma, dbeta);                                                              \
-  } while (0)
-  const bool quad = W % 4 == 0, al = quad && bn2d::aligned16(X) && bn2d::aligned16(dX);
-  if (bn2d::pool_small(H, W)) {
-    if (!quad) CLICA_POOL_BWD(bn2d::kPoolLdsSmall, 1, false);
-    else if (al) CLICA_POOL_BWD(bn2d::kPoolLdsSmall, 4, true);
-    else CLICA_POOL_BWD(bn2d::kPoolLdsSmall, 4, false);
-  } else {
-    if (!quad) CLICA_POOL_BWD(bn2d::kPoolLdsFloats, 1, false);
-    else if (al) CLICA_POOL_BWD(bn2d::kPoolLdsFloats, 4, true);
-    else CLICA_POOL_BWD(bn2d::kPoolLdsFloats, 4, false);
-  }
-#undef CLICA_POOL_BWD
+  bn2d::with_pool_instance(H, W, W % 4 == 0 && bn2d::aligned16(X) && bn2d::aligned16(dX), [&](auto i) {
+    hipLaunchKernelGGL((bn2d::pool_sums_k<i.LDSF, i.VEC, i.AL>), grid, block, 0, st, X, dP, gamma, beta, save_mean, save_invstd, N, (int)C, (int)H,
+                       (int)W, geo.per, slope, part);
+    hipLaunchKernelGGL((bn2d::pool_bwd_apply_k<i.LDSF, i.VEC, i.AL>), grid, block, 0, st, X, dP, gamma, beta, save_mean, save_invstd, N, (int)C,
+                       (int)H, (int)W, geo.per, Mf, slope, part, dX, dgamma, dbeta);
+  });
   return launch_status("clica_bn2d_act_maxpool_bwd");
 }
 

@@ -852,27 +852,35 @@ def r2_loss_bwd(y_pred: torch.Tensor, y: torch.Tensor, inv_var: torch.Tensor, g:
 # ------------------------------------------------------------------------------- BatchNorm1d / GroupNorm(1, C) + LeakyReLU
 NORM_KINDS = {"bn": 0, "gn": 1}                        # CLICA_NORM_BATCH / CLICA_NORM_GROUP
 
-# partial-sum workspaces of the norm kernels per (device, kind, M, C); as _R2_WS an entry is never replaced or freed, so a pointer a
-# captured graph recorded stays valid.  No initial contents are needed; one entry serves one launch at a time on one stream.
-_NORM_WS = {}
+# Partial-sum workspaces of the norm, bn2d and stem-unit kernels per (family, device, shape); as _R2_WS an entry is never replaced or
+# freed, so a pointer a captured graph recorded stays valid.  No initial contents are needed; one entry serves one launch at a time on
+# one stream.
+_PARTIAL_WS = {}
+
+
+def _partial_workspace(family: str, shape, device, size_fn: str, size_args, what: str) -> torch.Tensor:
+    """The cached workspace of `family` for `shape` on `device`.  The library's size_fn(*size_args, &bytes) gives its size (and validates
+    the shape); `what` names the workspace in the error of a first use under capture."""
+    device = torch.device(device)
+    key = (family, device.index if device.index is not None else torch.cuda.current_device()) + tuple(shape)
+    ws = _PARTIAL_WS.get(key)
+    if ws is None:
+        nb = C.c_size_t()
+        check(getattr(load(), size_fn)(*size_args, C.byref(nb)), size_fn)
+        if torch.cuda.is_current_stream_capturing():
+            # (memory allocated while capturing belongs to the graph's pool: not something to cache)
+            raise ClicaError(f"{what} yet -- run the step once eagerly before capturing it")
+        ws = _PARTIAL_WS[key] = torch.empty(max(nb.value, 16), dtype=torch.uint8, device=device)
+    _lib.note_graph_use(ws)
+    return ws
 
 
 def norm_workspace(kind: str, M: int, C_: int, device) -> torch.Tensor:
     """The cached workspace of clica_bn_lrelu_fwd_train / _bwd ("bn") or clica_gn_lrelu_bwd ("gn") for M x C on `device`."""
     if kind not in NORM_KINDS:
         raise ValueError(f"kind {kind!r} (one of {sorted(NORM_KINDS)})")
-    device = torch.device(device)
-    key = (device.index if device.index is not None else torch.cuda.current_device(), kind, int(M), int(C_))
-    ws = _NORM_WS.get(key)
-    if ws is None:
-        nb = C.c_size_t()
-        check(load().clica_norm_workspace_bytes(NORM_KINDS[kind], int(M), int(C_), 1.0, C.byref(nb)), "clica_norm_workspace_bytes")
-        if torch.cuda.is_current_stream_capturing():
-            # (memory allocated while capturing belongs to the graph's pool: not something to cache)
-            raise ClicaError(f"norm: no {kind} workspace for shape ({M}, {C_}) yet -- run the step once eagerly before capturing it")
-        ws = _NORM_WS[key] = torch.empty(max(nb.value, 16), dtype=torch.uint8, device=device)
-    _lib.note_graph_use(ws)
-    return ws
+    return _partial_workspace("norm", (kind, int(M), int(C_)), device, "clica_norm_workspace_bytes",
+                              (NORM_KINDS[kind], int(M), int(C_), 1.0), f"norm: no {kind} workspace for shape ({M}, {C_})")
 
 
 def _norm_mat(name: str, t: torch.Tensor) -> torch.Tensor:
@@ -889,6 +897,19 @@ def _norm_vec(name: str, t: torch.Tensor, n: int) -> torch.Tensor:
     return t
 
 
+def _running_pair(running_mean, running_var, n: int) -> None:
+    """The optional running statistics of a training forward: both or neither."""
+    if (running_mean is None) != (running_var is None):
+        raise ValueError("running_mean and running_var come together")
+    if running_mean is not None:
+        _norm_vec("running_mean", running_mean, n); _norm_vec("running_var", running_var, n)
+
+
+def _eval_vecs(weight, bias, running_mean, running_var, n: int) -> None:
+    for nm, t in (("weight", weight), ("bias", bias), ("running_mean", running_mean), ("running_var", running_var)):
+        _norm_vec(nm, t, n)
+
+
 def batchnorm_lrelu_fwd(x, weight, bias, running_mean=None, running_var=None, eps: float = 1e-5, momentum: float = 0.1,
                         slope: float = 0.01):
     """Training BatchNorm1d over the rows of x [M, C] (M >= 2) fused with LeakyReLU(slope) (slope = 1: none) in two launches
@@ -897,10 +918,7 @@ def batchnorm_lrelu_fwd(x, weight, bias, running_mean=None, running_var=None, ep
     x = _norm_mat("x", x)
     M, n = x.shape
     _norm_vec("weight", weight, n); _norm_vec("bias", bias, n)
-    if (running_mean is None) != (running_var is None):
-        raise ValueError("running_mean and running_var come together")
-    if running_mean is not None:
-        _norm_vec("running_mean", running_mean, n); _norm_vec("running_var", running_var, n)
+    _running_pair(running_mean, running_var, n)
     y = torch.empty_like(x)
     save_mean = torch.empty(n, dtype=torch.float32, device=x.device)
     save_invstd = torch.empty(n, dtype=torch.float32, device=x.device)
@@ -917,8 +935,7 @@ def batchnorm_lrelu_eval(x, weight, bias, running_mean, running_var, eps: float 
     """Inference BatchNorm1d on the running statistics fused with LeakyReLU(slope): one element-wise launch (clica_bn_lrelu_fwd_eval)."""
     x = _norm_mat("x", x)
     M, n = x.shape
-    for nm, t in (("weight", weight), ("bias", bias), ("running_mean", running_mean), ("running_var", running_var)):
-        _norm_vec(nm, t, n)
+    _eval_vecs(weight, bias, running_mean, running_var, n)
     y = torch.empty_like(x)
     check(load().clica_bn_lrelu_fwd_eval(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), running_mean.data_ptr(), running_var.data_ptr(),
                                          M, n, float(eps), float(slope), y.data_ptr(), stream_ptr()), "clica_bn_lrelu_fwd_eval")
@@ -977,25 +994,10 @@ def groupnorm_lrelu_bwd(x, y, dy, weight, mean, rstd, slope: float = 0.01):
 
 
 # ------------------------------------------------------------------------------- BatchNorm2d (+ residual) + (leaky) ReLU, NCHW
-# partial workspaces of the bn2d kernels per (device, N, C, HW); as _NORM_WS an entry is never replaced or freed, so a pointer a captured
-# graph recorded stays valid.  No initial contents are needed; one entry serves one launch at a time on one stream.
-_BN2D_WS = {}
-
-
 def bn2d_workspace(N: int, C_: int, HW: int, device) -> torch.Tensor:
     """The cached workspace of clica_bn2d_act_fwd_train / _bwd for x[N, C, H, W] with H W = HW on `device`."""
-    device = torch.device(device)
-    key = (device.index if device.index is not None else torch.cuda.current_device(), int(N), int(C_), int(HW))
-    ws = _BN2D_WS.get(key)
-    if ws is None:
-        nb = C.c_size_t()
-        check(load().clica_bn2d_workspace_bytes(int(N), int(C_), int(HW), C.byref(nb)), "clica_bn2d_workspace_bytes")
-        if torch.cuda.is_current_stream_capturing():
-            # (memory allocated while capturing belongs to the graph's pool: not something to cache)
-            raise ClicaError(f"bn2d: no workspace for shape ({N}, {C_}, {HW}) yet -- run the step once eagerly before capturing it")
-        ws = _BN2D_WS[key] = torch.empty(max(nb.value, 16), dtype=torch.uint8, device=device)
-    _lib.note_graph_use(ws)
-    return ws
+    shape = (int(N), int(C_), int(HW))
+    return _partial_workspace("bn2d", shape, device, "clica_bn2d_workspace_bytes", shape, f"bn2d: no workspace for shape ({N}, {C_}, {HW})")
 
 
 def _bn2d_map(name: str, t: torch.Tensor, shape=None) -> torch.Tensor:
@@ -1017,10 +1019,7 @@ def batchnorm2d_act_fwd(x, weight, bias, running_mean=None, running_var=None, ep
     if residual is not None:
         _bn2d_map("residual", residual, x.shape)
     _norm_vec("weight", weight, n); _norm_vec("bias", bias, n)
-    if (running_mean is None) != (running_var is None):
-        raise ValueError("running_mean and running_var come together")
-    if running_mean is not None:
-        _norm_vec("running_mean", running_mean, n); _norm_vec("running_var", running_var, n)
+    _running_pair(running_mean, running_var, n)
     ws = bn2d_workspace(N, n, H * W, x.device)       # (validates the shape)
     y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
     save_mean = torch.empty(n, dtype=torch.float32, device=x.device)
@@ -1039,8 +1038,7 @@ def batchnorm2d_act_eval(x, weight, bias, running_mean, running_var, eps: float 
     N, n, H, W = x.shape
     if residual is not None:
         _bn2d_map("residual", residual, x.shape)
-    for nm, t in (("weight", weight), ("bias", bias), ("running_mean", running_mean), ("running_var", running_var)):
-        _norm_vec(nm, t, n)
+    _eval_vecs(weight, bias, running_mean, running_var, n)
     y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
     check(load().clica_bn2d_act_fwd_eval(x.data_ptr(), ptr(residual), weight.data_ptr(), bias.data_ptr(), running_mean.data_ptr(),
                                          running_var.data_ptr(), N, n, H * W, float(eps), float(slope), y.data_ptr(), stream_ptr()),
@@ -1069,7 +1067,6 @@ def batchnorm2d_act_bwd(x, y, dy, weight, save_mean, save_invstd, slope: float =
 # ------------------------------------------------------------------------------- the stem unit with its max-pool; global average pool
 POOL_LDS_FLOATS = 112 * 112 + 56 * 56 + 56 * 56 // 8      # csrc/bn2d.h kPoolLdsFloats: a plane, its window gradients and argmax nibbles in LDS
 AVGPOOL_MAX_HW = 1 << 14                   # csrc/pool2d.hip avgpool::kMaxHW
-_POOL_WS = {}
 
 
 def maxpool_out_hw(H: int, W: int):
@@ -1084,18 +1081,10 @@ def bn2d_maxpool_fits(H: int, W: int) -> bool:
 
 
 def bn2d_maxpool_workspace(N: int, C_: int, H: int, W: int, device) -> torch.Tensor:
-    """The cached workspace of clica_bn2d_act_maxpool_fwd_train / _bwd for x[N, C, H, W] on `device` (the bn2d_workspace pattern)."""
-    device = torch.device(device)
-    key = (device.index if device.index is not None else torch.cuda.current_device(), int(N), int(C_), int(H), int(W))
-    ws = _POOL_WS.get(key)
-    if ws is None:
-        nb = C.c_size_t()
-        check(load().clica_bn2d_maxpool_workspace_bytes(int(N), int(C_), int(H), int(W), C.byref(nb)), "clica_bn2d_maxpool_workspace_bytes")
-        if torch.cuda.is_current_stream_capturing():
-            raise ClicaError(f"bn2d + max-pool: no workspace for shape ({N}, {C_}, {H}, {W}) yet -- run the step once eagerly before capturing it")
-        ws = _POOL_WS[key] = torch.empty(max(nb.value, 16), dtype=torch.uint8, device=device)
-    _lib.note_graph_use(ws)
-    return ws
+    """The cached workspace of clica_bn2d_act_maxpool_fwd_train / _bwd for x[N, C, H, W] on `device`."""
+    shape = (int(N), int(C_), int(H), int(W))
+    return _partial_workspace("pool", shape, device, "clica_bn2d_maxpool_workspace_bytes", shape,
+                              f"bn2d + max-pool: no workspace for shape ({N}, {C_}, {H}, {W})")
 
 
 def batchnorm2d_act_maxpool_fwd(x, weight, bias, running_mean=None, running_var=None, eps: float = 1e-5, momentum: float = 0.1,
@@ -1106,10 +1095,7 @@ def batchnorm2d_act_maxpool_fwd(x, weight, bias, running_mean=None, running_var=
     x = _bn2d_map("x", x)
     N, n, H, W = x.shape
     _norm_vec("weight", weight, n); _norm_vec("bias", bias, n)
-    if (running_mean is None) != (running_var is None):
-        raise ValueError("running_mean and running_var come together")
-    if running_mean is not None:
-        _norm_vec("running_mean", running_mean, n); _norm_vec("running_var", running_var, n)
+    _running_pair(running_mean, running_var, n)
     ws = bn2d_maxpool_workspace(N, n, H, W, x.device)       # (validates the shape)
     p = torch.empty((N, n) + maxpool_out_hw(H, W), dtype=torch.float32, device=x.device)
     save_mean = torch.empty(n, dtype=torch.float32, device=x.device)
@@ -1125,8 +1111,7 @@ def batchnorm2d_act_maxpool_eval(x, weight, bias, running_mean, running_var, eps
     """The same on the running statistics (inference): one launch (clica_bn2d_act_maxpool_fwd_eval)."""
     x = _bn2d_map("x", x)
     N, n, H, W = x.shape
-    for nm, t in (("weight", weight), ("bias", bias), ("running_mean", running_mean), ("running_var", running_var)):
-        _norm_vec(nm, t, n)
+    _eval_vecs(weight, bias, running_mean, running_var, n)
     p = torch.empty((N, n) + maxpool_out_hw(H, W), dtype=torch.float32, device=x.device)
     check(load().clica_bn2d_act_maxpool_fwd_eval(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), running_mean.data_ptr(),
                                                  running_var.data_ptr(), N, n, H, W, float(eps), float(slope), p.data_ptr(), stream_ptr()),

@@ -27,15 +27,23 @@ SHAPES = [(2, 3, 1, 1),        # M = 2 (dx not compared: ill-conditioned, as in 
           (5, 65, 3, 5),       # HW = 15; C not a multiple of 64
           (3, 24, 17, 13),     # HW = 221: scalar path, several waves per plane
           (2, 257, 7, 9),      # shape coverage
-          (16, 64, 16, 16),    # layer-1 geometry; several splits
-          (6, 40, 32, 32)]     # stem geometry, HW = 1024; multi-split merge
+          (16, 64, 16, 16),    # layer-1 geometry (one split: 16 images)
+          (6, 40, 32, 32),     # stem geometry, HW = 1024 (one split: 6144 values per channel)
+          # S > 1 (bn2d.h's geometry()): the later launch merges several partials in split order
+          (9, 3, 48, 48),      # plane, quads, S = 2: 5 + 4 images (ragged)
+          (5, 2, 63, 65),      # plane, scalar path, S = 2: 3 + 2 images
+          (37, 24, 4, 4),      # small, four pieces per channel, S = 3: 13 + 13 + 11 images
+          (18, 33, 2, 4),      # small, HW = 8: 66 pieces (a partial chunk), S = 2
+          (40, 70, 2, 2)]      # small, one piece per channel, partial chunk, S = 3: 14 + 14 + 12 images
 EVAL_SHAPES = [(3, 7, 2, 2), (5, 65, 3, 5), (4, 128, 8, 8)]
-UNALIGNED_SHAPES = [(8, 512, 2, 2), (4, 128, 8, 8)]      # HW % 4 == 0: the scalar accesses keep the reduction order, so the same bits
+# HW % 4 == 0: the scalar accesses keep the reduction order, so the same bits
+UNALIGNED_SHAPES = [(8, 512, 2, 2), (4, 128, 8, 8), (9, 3, 48, 48), (37, 24, 4, 4)]
 
 # A case whose first draw leaves out more than MAX_LEFT_OUT of its channels (at slope 0 / 0.01: the same z), or is conditioned worse than
 # MAX_KAPPA, takes the next attempt that is not: (N, C, H, W, cls, residual) -> attempt.  Found once by `python tests/bn2d_oracle.py`
 # from the inputs and the fp64 oracle alone; both properties are asserted by tests/test_bn2d_host.py.
-SEED_ATTEMPT = {(2, 3, 1, 1, 1, False): 1, (2, 3, 1, 1, 1, True): 1, (6, 40, 32, 32, 0, False): 1, (6, 40, 32, 32, 1, False): 1}
+SEED_ATTEMPT = {(2, 3, 1, 1, 1, False): 1, (2, 3, 1, 1, 1, True): 1, (6, 40, 32, 32, 0, False): 1, (6, 40, 32, 32, 1, False): 1,
+                (9, 3, 48, 48, 1, False): 1, (9, 3, 48, 48, 1, True): 1}
 MAX_ATTEMPTS = 6
 
 # seeds of the BasicBlock cases (inplanes, planes, stride) -> seed: the first for which the fp64 block has no pre-activation within

@@ -31,10 +31,14 @@ SHAPES = [(2, 3, 1, 1),          # M = 2: dx not compared, as in the BatchNorm2d
           (3, 5, 7, 9),          # odd, non-square, scalar path
           (2, 4, 5, 5),          # odd square plane
           (2, 65, 8, 8),         # C not a multiple of 64
-          (6, 40, 32, 32),       # stem geometry, several splits
-          (1, 2, 112, 112)]      # the largest plane of the contract
+          (6, 40, 32, 32),       # stem geometry (one split: 6144 values per channel)
+          (1, 2, 112, 112),      # the largest plane of the contract
+          # S = 2 (bn2d.h's geometry()): the later launch merges two partials in split order
+          (9, 3, 48, 48),        # 16 KB LDS instance, quads
+          (5, 2, 64, 64),        # 64 KB LDS instance, quads
+          (5, 2, 63, 65)]        # 64 KB LDS instance, scalar path
 EVAL_SHAPES = [(3, 5, 7, 9), (2, 65, 8, 8), (1, 2, 112, 112)]
-UNALIGNED_SHAPES = [(2, 65, 8, 8), (6, 40, 32, 32)]      # W % 4 == 0: the 16-byte path when aligned
+UNALIGNED_SHAPES = [(2, 65, 8, 8), (6, 40, 32, 32), (9, 3, 48, 48)]      # W % 4 == 0: the 16-byte path when aligned
 
 # A case whose first draw leaves out more than MAX_LEFT_OUT of its channels, is conditioned worse than MAX_KAPPA or has a gap under
 # MIN_GAP_REL takes the next attempt that does not: (N, C, H, W, cls) -> attempt.  Found once by `python tests/pool2d_oracle.py`
