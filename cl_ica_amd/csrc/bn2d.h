@@ -69,10 +69,97 @@ static inline int64_t pool_lds_floats(int32_t H, int32_t W) {
 static inline bool pool_fits(int32_t H, int32_t W) { return H >= 1 && W >= 1 && pool_lds_floats(H, W) <= kPoolLdsFloats; }
 static inline bool pool_small(int32_t H, int32_t W) { return pool_lds_floats(H, W) <= kPoolLdsSmall; }
 
+// ------------------------------------------------------------------------------------------------ channels-last (bn2d_nhwc.hip)
+// Dense NHWC activations are the row-major matrix x[M = N H W, C], row = pixel.  "rows" geometry, from (M, C) alone:
+//   a lane owns `vec` consecutive channels of a row (4 when C % 4 == 0: one 16-byte access when the pointers are aligned; else 1) and
+//   walks down the rows; `lpr` lanes (a power of two <= 64) cover a row or a 64-lane chunk of it, so a wave covers 64 / lpr consecutive
+//   rows -- at C = 64 one contiguous KB -- and the 4 waves of a workgroup `rps` = 256 / lpr rows per step.  grid.x = chunks of lpr lanes.
+//   statistics / sums launches: grid.y = S row splits of `per` rows, sized for kRowsSplitSteps steps of a workgroup.  Every apply
+//     workgroup merges the S partials of its lpr * vec channels again, `mg` = 256 / (lpr vec) threads per channel, each the `ms` splits
+//     of its range in split order, then the ranges in range order through LDS: S <= kRowsMergeLoads * mg (<= kRowsMaxSplits) keeps that
+//     at kRowsMergeLoads / 8 rounds of loads whatever C is, and lets C = 64 -- where one chunk is the whole row -- have 256 splits.
+//     The T workgroups of an apply launch read T S C 12 bytes of partials between them, from L2: with S <= 512 and 2048 tiles that was
+//     0.8 GB at ResNet-18's C = 64 layers and cost more than the statistics launch gained (profiles/c4_nhwc_summary.md), hence these caps.
+//   apply / backward-apply launches: grid.y = T row tiles of `tile` rows, as many as fill the part (kRowsMaxTiles workgroups), at least
+//     kRowsTileSteps steps each so that the merge is paid for; the tiles are element-wise work and shape no reduction.
+constexpr int kRowsMaxSplits = 256;
+constexpr int kRowsMergeLoads = 64;           // partials per channel one thread of an apply workgroup merges, at most
+constexpr int kRowsSplitSteps = 32;           // rows a lane takes in a split before the cap on S
+constexpr int kRowsTileSteps = 8;             // rows a lane takes in a tile, at least
+constexpr int kRowsMaxTiles = 1024;           // apply workgroups: 256 CUs x 4
+
+struct Rows {
+  int vec, lpr, rps, chunks;      // channels per lane; lanes per row (chunk); rows per workgroup step; grid.x
+  int mg, ms;                     // merge: threads per channel, splits per thread
+  int S;                          // row splits = partials per channel
+  int64_t per;                    // rows per split (the last one may hold fewer)
+  int T;                          // row tiles of the apply launches
+  int64_t tile;                   // rows per tile, a multiple of rps
+};
+
+static inline Rows rows_geometry(int64_t M, int32_t C) {
+  Rows g;
+  g.vec = C % 4 == 0 ? 4 : 1;
+  const int U = C / g.vec;
+  g.lpr = 1;
+  while (g.lpr < U && g.lpr < 64) g.lpr *= 2;
+  g.rps = kThreads / g.lpr;
+  g.chunks = (int)ceil_div((int64_t)U, (int64_t)g.lpr);
+  g.mg = kThreads / (g.lpr * g.vec);        // (lpr = 64, vec = 4: a thread per channel)
+  int64_t cap = (int64_t)kRowsMergeLoads * g.mg;
+  if (cap > kRowsMaxSplits) cap = kRowsMaxSplits;
+  int64_t s = ceil_div(M, (int64_t)kRowsSplitSteps * g.rps);
+  if (s > cap) s = cap;
+  if (s < 1) s = 1;
+  g.per = ceil_div(M, s);
+  g.S = (int)ceil_div(M, g.per);            // no empty split
+  g.ms = (int)ceil_div((int64_t)g.S, (int64_t)g.mg);
+  int64_t tiles = kRowsMaxTiles / g.chunks;
+  if (tiles < 1) tiles = 1;
+  int64_t t = ceil_div(M, tiles);
+  if (t < (int64_t)kRowsTileSteps * g.rps) t = (int64_t)kRowsTileSteps * g.rps;
+  g.tile = ceil_div(t, (int64_t)g.rps) * g.rps;
+  g.T = (int)ceil_div(M, g.tile);
+  return g;
+}
+
+// forward: three planes [S][C] (count, mean, M2 of x - x[0, c]); backward: two (sum dz, sum dz xhat) in the same buffer
+static inline size_t rows_workspace_bytes(int64_t M, int32_t C) {
+  return align_up((size_t)3 * (size_t)rows_geometry(M, C).S * (size_t)C * sizeof(float), 16);
+}
+
 // the statistics launch of clica_bn2d_act_fwd_train (bn2d.hip): partials [3][S][C] of geometry(N, HW) into `part`
 void launch_stats(hipStream_t st, const float* X, int64_t N, int32_t C, int32_t HW, float* part);
 
 #ifdef __HIPCC__
+using r2::Stat;
+using r2::stat_add;
+using r2::stat_merge;
+
+// K values (already minus the pivot) into a: their own mean and M2, then Chan's merge
+template <int K>
+__device__ __forceinline__ void stat_block(Stat& a, const float* d) {
+  if (K == 1) {
+    stat_add(a, d[0], 0.f);
+    return;
+  }
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) s += d[k];
+  const float m = s * (1.f / K);
+  float q = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const float e = d[k] - m;
+    q = fmaf(e, e, q);
+  }
+  stat_merge(a, Stat{(float)K, m, q, 0.f});
+}
+
+__device__ __forceinline__ Stat shfl_down_stat(const Stat& s, int off) {
+  return Stat{__shfl_down(s.cnt, off, 64), __shfl_down(s.mean, off, 64), __shfl_down(s.m2, off, 64), 0.f};
+}
+
 // VEC consecutive values; AL: one 16-byte access (the pointer is aligned), else scalar accesses of the same values
 template <int VEC, bool AL>
 __device__ __forceinline__ void load(const float* __restrict__ p, float* v) {

@@ -17,34 +17,6 @@
 namespace clica {
 namespace bn2d {
 
-using r2::Stat;
-using r2::stat_add;
-using r2::stat_merge;
-
-// K values (already minus the pivot) into a: their own mean and M2, then Chan's merge
-template <int K>
-__device__ __forceinline__ void stat_block(Stat& a, const float* d) {
-  if (K == 1) {
-    stat_add(a, d[0], 0.f);
-    return;
-  }
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < K; ++k) s += d[k];
-  const float m = s * (1.f / K);
-  float q = 0.f;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const float e = d[k] - m;
-    q = fmaf(e, e, q);
-  }
-  stat_merge(a, Stat{(float)K, m, q, 0.f});
-}
-
-__device__ __forceinline__ Stat shfl_down_stat(const Stat& s, int off) {
-  return Stat{__shfl_down(s.cnt, off, 64), __shfl_down(s.mean, off, 64), __shfl_down(s.m2, off, 64), 0.f};
-}
-
 // the lanes of a wave, then the waves of the workgroup in wave order: thread 0 ends with the workgroup's statistic
 __device__ __forceinline__ void block_merge(Stat& s, float* sh /*[kWaves * 3]*/) {
 #pragma unroll

@@ -105,6 +105,41 @@ __device__ __forceinline__ void merge_sums(const float* __restrict__ part, int S
   }
 }
 
+// The splits [s0, s1) of the S alone, in split order: what one of several threads that share a channel's merge takes (bn2d_nhwc.hip).
+// Siblings rather than the general case of the two above, whose code -- and with it the contraction choices behind them -- stays as it is.
+__device__ __forceinline__ Stat merge_stats_range(const float* __restrict__ part, int S, int C, int c, int s0, int s1) {
+  const size_t plane = (size_t)S * C;
+  Stat t{0.f, 0.f, 0.f, 0.f};
+  for (int i0 = s0; i0 < s1; i0 += 8) {
+    float a[8], m[8], q[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float* p = part + (size_t)(i0 + j < s1 ? i0 + j : s1 - 1) * C + c;
+      a[j] = p[0]; m[j] = p[plane]; q[j] = p[2 * plane];
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (i0 + j < s1) stat_merge(t, Stat{a[j], m[j], q[j], 0.f});
+  }
+  return t;
+}
+
+__device__ __forceinline__ void merge_sums_range(const float* __restrict__ part, int S, int C, int c, int s0, int s1, float& s1_, float& s2_) {
+  const size_t plane = (size_t)S * C;
+  s1_ = 0.f; s2_ = 0.f;
+  for (int i0 = s0; i0 < s1; i0 += 8) {
+    float a[8], b[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const bool in = i0 + j < s1;
+      const float* p = part + (size_t)(in ? i0 + j : s1 - 1) * C + c;
+      a[j] = in ? p[0] : 0.f; b[j] = in ? p[plane] : 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { s1_ += a[j]; s2_ += b[j]; }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ lane = column: the waves of a workgroup
 // Every wave holds a value per lane (column); the lanes of wave 0 whose column is `active` end with the workgroup's, merged in wave
 // order.  All threads call (a barrier).

@@ -1157,6 +1157,123 @@ def avgpool2d_global_bwd(dy, H: int, W: int):
     return dx
 
 
+# ------------------------------------------------------------------------------- the same units on dense channels-last activations
+def bn2d_nhwc_workspace(M: int, C_: int, device) -> torch.Tensor:
+    """The cached workspace of clica_bn2d_nhwc_act_fwd_train / _bwd for a channels-last x[N, C, H, W] with N H W = M on `device`."""
+    shape = (int(M), int(C_))
+    return _partial_workspace("bn2d_nhwc", shape, device, "clica_bn2d_nhwc_workspace_bytes", shape,
+                              f"bn2d (channels-last): no workspace for shape ({M}, {C_})")
+
+
+def _bn2d_nhwc_map(name: str, t: torch.Tensor, shape=None) -> torch.Tensor:
+    """A 4-D tensor whose memory is the dense row-major [N, H, W, C] (with C = 1 or H = W = 1 that is also the memory of a contiguous
+    NCHW tensor, whatever its strides say).  Layout and shape only: _nhwc_on_gpu comes after every such check of a call."""
+    if t.dim() != 4 or t.numel() == 0 or not t.is_contiguous(memory_format=torch.channels_last):
+        raise ValueError(f"{name} must be a dense channels-last tensor [N, C, H, W] (strides (H W C, 1, W C, C)), got shape {tuple(t.shape)} "
+                         f"strides {t.stride()}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} {tuple(t.shape)} must have the shape of x {tuple(shape)}")
+    return t
+
+
+def _nhwc_vecs(n: int, **vecs) -> None:
+    for name, t in vecs.items():
+        if t is not None and (t.numel() != n or not t.is_contiguous()):
+            raise ValueError(f"{name} must hold {n} contiguous values, got {tuple(t.shape)}")
+
+
+def _nhwc_on_gpu(**tensors) -> None:
+    for name, t in tensors.items():
+        if t is not None:
+            require_cuda(t, name)
+
+
+def _empty_nhwc(shape, device) -> torch.Tensor:
+    return torch.empty(tuple(shape), dtype=torch.float32, device=device, memory_format=torch.channels_last)
+
+
+def batchnorm2d_act_fwd_nhwc(x, weight, bias, running_mean=None, running_var=None, eps: float = 1e-5, momentum: float = 0.1,
+                             slope: float = 0.0, residual=None):
+    """batchnorm2d_act_fwd on a dense channels-last x (N H W >= 2) and residual: two launches (clica_bn2d_nhwc_act_fwd_train).
+    Returns (y, save_mean [C], save_invstd [C]), y channels-last.  Anything but dense channels-last maps of one shape and vectors of C
+    values: ValueError, before any launch."""
+    x = _bn2d_nhwc_map("x", x)
+    N, n, H, W = x.shape
+    if residual is not None:
+        _bn2d_nhwc_map("residual", residual, x.shape)
+    if (running_mean is None) != (running_var is None):
+        raise ValueError("running_mean and running_var come together")
+    _nhwc_vecs(n, weight=weight, bias=bias, running_mean=running_mean, running_var=running_var)
+    _nhwc_on_gpu(x=x, residual=residual, weight=weight, bias=bias, running_mean=running_mean, running_var=running_var)
+    M = N * H * W
+    ws = bn2d_nhwc_workspace(M, n, x.device)       # (validates the shape; M = 1 is the training call's to refuse)
+    y = _empty_nhwc(x.shape, x.device)
+    save_mean = torch.empty(n, dtype=torch.float32, device=x.device)
+    save_invstd = torch.empty(n, dtype=torch.float32, device=x.device)
+    check(load().clica_bn2d_nhwc_act_fwd_train(x.data_ptr(), ptr(residual), weight.data_ptr(), bias.data_ptr(), M, n, float(eps),
+                                               float(momentum), float(slope), y.data_ptr(), save_mean.data_ptr(), save_invstd.data_ptr(),
+                                               ptr(running_mean), ptr(running_var), ws.data_ptr(), ws.numel(), stream_ptr()),
+          "clica_bn2d_nhwc_act_fwd_train")
+    return y, save_mean, save_invstd
+
+
+def batchnorm2d_act_eval_nhwc(x, weight, bias, running_mean, running_var, eps: float = 1e-5, slope: float = 0.0, residual=None):
+    """batchnorm2d_act_eval on a dense channels-last x and residual: one element-wise launch (clica_bn2d_nhwc_act_fwd_eval)."""
+    x = _bn2d_nhwc_map("x", x)
+    N, n, H, W = x.shape
+    if residual is not None:
+        _bn2d_nhwc_map("residual", residual, x.shape)
+    _nhwc_vecs(n, weight=weight, bias=bias, running_mean=running_mean, running_var=running_var)
+    _nhwc_on_gpu(x=x, residual=residual, weight=weight, bias=bias, running_mean=running_mean, running_var=running_var)
+    y = _empty_nhwc(x.shape, x.device)
+    check(load().clica_bn2d_nhwc_act_fwd_eval(x.data_ptr(), ptr(residual), weight.data_ptr(), bias.data_ptr(), running_mean.data_ptr(),
+                                              running_var.data_ptr(), N * H * W, n, float(eps), float(slope), y.data_ptr(), stream_ptr()),
+          "clica_bn2d_nhwc_act_fwd_eval")
+    return y
+
+
+def batchnorm2d_act_bwd_nhwc(x, y, dy, weight, save_mean, save_invstd, slope: float = 0.0, need_dr: bool = False):
+    """(dx, dr, dweight, dbias) of batchnorm2d_act_fwd_nhwc from dense channels-last x, y (its OUTPUT: the gate) and dy: two launches
+    (clica_bn2d_nhwc_act_bwd).  dx and dr are channels-last; dr is None unless `need_dr`."""
+    x = _bn2d_nhwc_map("x", x)
+    _bn2d_nhwc_map("y", y, x.shape); _bn2d_nhwc_map("dy", dy, x.shape)
+    N, n, H, W = x.shape
+    _nhwc_vecs(n, weight=weight, save_mean=save_mean, save_invstd=save_invstd)
+    _nhwc_on_gpu(x=x, y=y, dy=dy, weight=weight, save_mean=save_mean, save_invstd=save_invstd)
+    M = N * H * W
+    ws = bn2d_nhwc_workspace(M, n, x.device)
+    dx = _empty_nhwc(x.shape, x.device)
+    dr = _empty_nhwc(x.shape, x.device) if need_dr else None
+    dw = torch.empty(n, dtype=torch.float32, device=x.device)
+    db = torch.empty(n, dtype=torch.float32, device=x.device)
+    check(load().clica_bn2d_nhwc_act_bwd(x.data_ptr(), y.data_ptr(), dy.data_ptr(), weight.data_ptr(), save_mean.data_ptr(),
+                                         save_invstd.data_ptr(), M, n, float(slope), dx.data_ptr(), ptr(dr), dw.data_ptr(), db.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), stream_ptr()), "clica_bn2d_nhwc_act_bwd")
+    return dx, dr, dw, db
+
+
+def avgpool2d_global_fwd_nhwc(x):
+    """flatten(adaptive_avg_pool2d(x, 1), 1) of a dense channels-last x: y [N, C], one launch (clica_avgpool2d_global_nhwc_fwd)."""
+    x = _bn2d_nhwc_map("x", x)
+    _nhwc_on_gpu(x=x)
+    N, n, H, W = x.shape
+    y = torch.empty((N, n), dtype=torch.float32, device=x.device)
+    check(load().clica_avgpool2d_global_nhwc_fwd(x.data_ptr(), N, H * W, n, y.data_ptr(), stream_ptr()), "clica_avgpool2d_global_nhwc_fwd")
+    return y
+
+
+def avgpool2d_global_bwd_nhwc(dy, H: int, W: int):
+    """dx [N, C, H, W], dense channels-last, = dy [N, C] / (H W) on every pixel: one launch (clica_avgpool2d_global_nhwc_bwd)."""
+    if dy.dim() != 2 or not dy.is_contiguous():
+        raise ValueError(f"dy must be a contiguous matrix [N, C], got shape {tuple(dy.shape)} strides {dy.stride()}")
+    require_cuda(dy, "dy")
+    N, n = dy.shape
+    dx = _empty_nhwc((N, n, int(H), int(W)), dy.device)
+    check(load().clica_avgpool2d_global_nhwc_bwd(dy.data_ptr(), N, int(H) * int(W), n, dx.data_ptr(), stream_ptr()),
+          "clica_avgpool2d_global_nhwc_bwd")
+    return dx
+
+
 def tick(counter: torch.Tensor):
     check(load().clica_tick(counter.data_ptr(), stream_ptr()), "clica_tick")
 

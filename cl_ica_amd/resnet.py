@@ -10,12 +10,19 @@ config 4 prescribes ("conv path via PyTorch-ROCm + HIP loss").
 Everything between the convolutions -- BatchNorm2d, the shortcut add, the ReLU -- is one call of the fused kernels of csrc/bn2d.hip per
 unit (``bn1 + relu``, ``bn2 (+ shortcut) + relu``, ``downsample[1]``) whenever ``_bn2d_on_hip`` holds: NORM_MODE "hip", a contiguous
 (NCHW) fp32 CUDA input, an affine module that tracks running statistics with a momentum, in training or in inference outside autograd.
-Anything else -- channels-last inputs among it -- runs the modules' own forward and torch's ``relu`` / ``+``.  The modules stay plain
-``nn.BatchNorm2d`` objects that own weight, bias, running_mean, running_var and num_batches_tracked: the state dict does not change.
+Anything else -- channels-last inputs among it, by default -- runs the modules' own forward and torch's ``relu`` / ``+``.  The modules
+stay plain ``nn.BatchNorm2d`` objects that own weight, bias, running_mean, running_var and num_batches_tracked: the state dict does not
+change.
 
 With POOL_MODE "hip" (and NORM_MODE "hip") the two pools run on csrc/pool2d.hip as well: the stem's ``bn1 + relu + maxpool`` is one
 unit that never writes the 32 x 32 activation, pooling indices or their sparse gradient (``_stem_pool_on_hip``: a plain
 ``nn.MaxPool2d(3, 2, 1)`` and a plane within the kernels' limit), and ``avgpool + flatten`` is one launch (``_avgpool_on_hip``).
+
+With NHWC_MODE "hip" (and NORM_MODE "hip") a dense channels-last input -- ``model.to(memory_format=torch.channels_last)`` -- takes the
+same units on the kernels of csrc/bn2d_nhwc.hip, whose outputs and gradients are channels-last again, so the backbone stays NHWC between
+MIOpen's convolutions; the average pool follows under POOL_MODE "hip".  A residual in the other layout runs torch's path (no hidden
+copy), and the stem's max-pool is the unit followed by ``nn.MaxPool2d`` (the fused stem kernel holds NCHW planes in LDS).  The default
+is "torch": channels-last inputs run the modules' own forward, as they always did.
 """
 from __future__ import annotations
 
@@ -40,6 +47,14 @@ POOL_MODE = os.environ.get("CLICA_RESNET_POOL", "hip")
 if POOL_MODE not in ("hip", "torch"):
     raise ValueError(f"CLICA_RESNET_POOL={POOL_MODE!r} (one of 'hip', 'torch')")
 
+# "hip": dense channels-last inputs take the bn2d units (and, under POOL_MODE "hip", the average pool) on csrc/bn2d_nhwc.hip where
+# NORM_MODE is "hip"; "torch": they run the modules' own forward, as before.  Read at call time.
+NHWC_MODE = os.environ.get("CLICA_RESNET_NHWC", "torch")
+if NHWC_MODE not in ("hip", "torch"):
+    raise ValueError(f"CLICA_RESNET_NHWC={NHWC_MODE!r} (one of 'hip', 'torch')")
+
+_NHWC = torch.channels_last
+
 
 class _BN2dActFn(torch.autograd.Function):
     """nn.BatchNorm2d in training mode + the shortcut add + the ReLU behind it (slope = 1: none) on clica_bn2d_act_fwd_train / _bwd.
@@ -59,6 +74,26 @@ class _BN2dActFn(torch.autograd.Function):
         x, y, weight, save_mean, save_invstd = ctx.saved_tensors
         dx, dr, dw, db = ops.batchnorm2d_act_bwd(x, y, gy.contiguous(), weight, save_mean, save_invstd, ctx.slope,
                                                  need_dr=ctx.needs_input_grad[1])
+        return dx, dr, dw, db, None, None
+
+
+class _BN2dActNhwcFn(torch.autograd.Function):
+    """_BN2dActFn on dense channels-last x (and r): clica_bn2d_nhwc_act_fwd_train / _bwd.  Output and input gradients are channels-last."""
+
+    @staticmethod
+    def forward(ctx, x, r, weight, bias, mod, slope):
+        y, save_mean, save_invstd = ops.batchnorm2d_act_fwd_nhwc(x, weight, bias, mod.running_mean, mod.running_var, mod.eps, mod.momentum,
+                                                                 slope, residual=r)
+        ctx.save_for_backward(x, y, weight, save_mean, save_invstd)
+        ctx.slope = slope
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x, y, weight, save_mean, save_invstd = ctx.saved_tensors
+        dx, dr, dw, db = ops.batchnorm2d_act_bwd_nhwc(x, y, gy.contiguous(memory_format=_NHWC), weight, save_mean, save_invstd, ctx.slope,
+                                                      need_dr=ctx.needs_input_grad[1])
         return dx, dr, dw, db, None, None
 
 
@@ -96,11 +131,39 @@ class _GlobalAvgPoolFn(torch.autograd.Function):
         return ops.avgpool2d_global_bwd(gy.contiguous(), *ctx.hw)
 
 
+class _GlobalAvgPoolNhwcFn(torch.autograd.Function):
+    """_GlobalAvgPoolFn on a dense channels-last x: clica_avgpool2d_global_nhwc_fwd / _bwd."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.hw = (x.shape[2], x.shape[3])
+        return ops.avgpool2d_global_fwd_nhwc(x)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        return ops.avgpool2d_global_bwd_nhwc(gy.contiguous(), *ctx.hw)
+
+
+def _layout(x):
+    """"nchw" for a contiguous tensor (those with C = 1 or H = W = 1, the same memory in both layouts, among them), "nhwc" for any other
+    dense channels-last tensor when NHWC_MODE is "hip", else None: not the kernels' input."""
+    if x.is_contiguous():
+        return "nchw"
+    if NHWC_MODE == "hip" and x.numel() > 0 and x.is_contiguous(memory_format=_NHWC):
+        return "nhwc"
+    return None
+
+
+def _same_layout(r, layout) -> bool:
+    return r.is_contiguous() if layout == "nchw" else r.is_contiguous(memory_format=_NHWC)
+
+
 def _bn2d_on_hip(m, x, r=None) -> bool:
     """Do the bn2d kernels cover this module on this input (and residual)?  Anything else runs the module's own forward, as before."""
-    if NORM_MODE != "hip" or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
+    if NORM_MODE != "hip" or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or _layout(x) is None:
         return False
-    if r is not None and not (r.is_cuda and r.dtype == torch.float32 and r.shape == x.shape and r.is_contiguous()):
+    if r is not None and not (r.is_cuda and r.dtype == torch.float32 and r.shape == x.shape and _same_layout(r, _layout(x))):
         return False
     if not (isinstance(m, nn.BatchNorm2d) and m.affine and m.track_running_stats and m.momentum is not None and x.shape[1] == m.num_features):
         return False
@@ -120,6 +183,12 @@ def _unit(bn, relu, x, r=None):
             y = y + r
         return y if relu is None else relu(y)
     slope = 1.0 if relu is None else 0.0
+    if _layout(x) == "nhwc":
+        if bn.training:
+            ops.bn2d_nhwc_workspace(x.shape[0] * x.shape[2] * x.shape[3], x.shape[1], x.device)     # (raises while capturing without a warm-up)
+            bn.num_batches_tracked.add_(1)
+            return _BN2dActNhwcFn.apply(x, r, bn.weight, bn.bias, bn, slope)
+        return ops.batchnorm2d_act_eval_nhwc(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.eps), slope, residual=r)
     if bn.training:
         ops.bn2d_workspace(x.shape[0], x.shape[1], x.shape[2] * x.shape[3], x.device)   # (raises while capturing without a warm-up: before anything is counted)
         bn.num_batches_tracked.add_(1)                      # in place on the device: capturable
@@ -129,7 +198,7 @@ def _unit(bn, relu, x, r=None):
 
 def _stem_pool_on_hip(bn, pool, x) -> bool:
     """Does the fused stem unit cover bn + relu + `pool` on this input?  Otherwise: the unfused unit, then the module."""
-    if POOL_MODE != "hip" or not _bn2d_on_hip(bn, x):
+    if POOL_MODE != "hip" or not _bn2d_on_hip(bn, x) or _layout(x) != "nchw":      # (the fused stem kernel holds NCHW planes in LDS)
         return False
     one = lambda v, k: v == k or v == (k, k)
     if not (type(pool) is nn.MaxPool2d and one(pool.kernel_size, 3) and one(pool.stride, 2) and one(pool.padding, 1) and one(pool.dilation, 1)
@@ -152,7 +221,7 @@ def _stem(bn, relu, pool, x):
 def _avgpool_on_hip(pool, x) -> bool:
     if POOL_MODE != "hip" or NORM_MODE != "hip":
         return False
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous() and x.numel() > 0):
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and _layout(x) is not None and x.numel() > 0):
         return False
     return type(pool) is nn.AdaptiveAvgPool2d and pool.output_size in (1, (1, 1)) and x.shape[2] * x.shape[3] <= ops.AVGPOOL_MAX_HW
 
@@ -208,7 +277,7 @@ class ResNet18(nn.Module):
             x = _stem(self.bn1, self.relu, self.maxpool, self.conv1(x))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         if _avgpool_on_hip(self.avgpool, x):
-            return self.fc(_GlobalAvgPoolFn.apply(x))
+            return self.fc((_GlobalAvgPoolNhwcFn if _layout(x) == "nhwc" else _GlobalAvgPoolFn).apply(x))
         return self.fc(torch.flatten(self.avgpool(x), 1))
 
 

@@ -750,6 +750,36 @@ int clica_bn2d_act_maxpool_bwd(const float* X, const float* dP, const float* gam
 int clica_avgpool2d_global_fwd(const float* X, int64_t rows, int32_t HW, float* Y, clica_stream_t stream);
 int clica_avgpool2d_global_bwd(const float* dY, int64_t rows, int32_t HW, float* dX, clica_stream_t stream);
 
+/* The same unit, Z = gamma xhat + beta (+ R), Y = lrelu(Z, slope), on DENSE CHANNELS-LAST activations: an NHWC tensor [N, H, W, C] is the
+ * row-major fp32 matrix X[M = N H W, C], row = pixel, statistics over the M rows of a column.  Mathematics, arguments, return codes and
+ * the workspace rules are those of clica_bn2d_act_*: training needs M >= 2, inference M >= 1, slope >= 0, 1 <= C <= 2^20.
+ * Geometry (from M and C alone, never from the pointers): a lane owns 4 consecutive channels when C % 4 == 0 (one 16-byte access per
+ * row when every tensor is 16-byte aligned, else scalar accesses of the same values in the same order: the same bits), otherwise 1;
+ * L = the power of two >= min(C / 4 | C, 64) lanes cover a row, a wave 64 / L consecutive rows, a workgroup of 4 waves 256 / L rows per
+ * step, grid.x = chunks of L lanes along C.  Training forward, two launches: Welford / Chan partials of X - X[0, c] per (row split,
+ * channel) -- per lane over its rows in order, the lanes of a wave that share a channel by shuffles, the waves through LDS in wave
+ * order --, then an apply launch over row tiles (as many as fill the part; independent of the S <= 256 splits) in which every
+ * workgroup merges the S partials of its channels in split order, shared among its threads in fixed ranges.  Backward: the same pair
+ * for (sum dZ, sum dZ xhat).  save_mean, save_invstd, the running statistics, dgamma and dbeta are written once, by tile 0.
+ * No floating-point atomics, no in-kernel counters.  clica_bn2d_nhwc_workspace_bytes is host-only: -1 for M < 1, C < 1, bytes == NULL. */
+int clica_bn2d_nhwc_workspace_bytes(int64_t M, int32_t C, size_t* bytes);
+int clica_bn2d_nhwc_act_fwd_train(const float* X, const float* R /*or NULL*/, const float* gamma, const float* beta, int64_t M, int32_t C,
+                                  float eps, float momentum, float slope, float* Y, float* save_mean, float* save_invstd,
+                                  float* running_mean /*[C] or NULL*/, float* running_var /*[C] or NULL*/, void* workspace,
+                                  size_t workspace_bytes, clica_stream_t stream);
+int clica_bn2d_nhwc_act_fwd_eval(const float* X, const float* R /*or NULL*/, const float* gamma, const float* beta,
+                                 const float* running_mean, const float* running_var, int64_t M, int32_t C, float eps, float slope,
+                                 float* Y, clica_stream_t stream);
+int clica_bn2d_nhwc_act_bwd(const float* X, const float* Y, const float* dY, const float* gamma, const float* save_mean,
+                            const float* save_invstd, int64_t M, int32_t C, float slope, float* dX, float* dR /*or NULL*/, float* dgamma,
+                            float* dbeta, void* workspace, size_t workspace_bytes, clica_stream_t stream);
+
+/* Global average pool of dense channels-last fp32 X[N, HW, C]: Y[n, c] = (X[n, 0, c] + X[n, 1, c] + ... in pixel order) x (1 / HW), a
+ * thread per (n, c) with the lanes along C, and its backward dX[n, k, c] = dY[n, c] x (1 / HW).  One launch each.
+ * 1 <= HW <= 16384, 1 <= C <= 2^20, N >= 1. */
+int clica_avgpool2d_global_nhwc_fwd(const float* X, int64_t N, int32_t HW, int32_t C, float* Y, clica_stream_t stream);
+int clica_avgpool2d_global_nhwc_bwd(const float* dY, int64_t N, int32_t HW, int32_t C, float* dX, clica_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Convolution stack of the KITTI-masks encoder  --  BetaVAE_H, /root/reference/kitti_masks/model.py:41-56:
  * Conv2d(k = 4, stride 2, pad 1) + ReLU stages as implicit GEMMs (fp32 MFMA, csrc/linear.hip, conv section), channels-last.

@@ -1,0 +1,206 @@
+#!/usr/bin/env python3
+"""Memory-format A/B of bench.py's c4 step (3DIdent train_step, ResNet-18 on (1024, 3, 64, 64) x 2 views) in ONE process (GPU box):
+
+    (a) nchw        contiguous model and inputs: bench.py's own leg, the baseline
+    (b) nhwc-torch  channels_last model and inputs, CLICA_RESNET_NHWC=torch: torch's / MIOpen's own BatchNorm, ReLU, add
+    (c) nhwc-hip    channels_last model and inputs, CLICA_RESNET_NHWC=hip: the units of csrc/bn2d_nhwc.hip
+
+  python tools/c4_layout_ab.py                      a throw-away run of every leg (MIOpen's find step), then two rounds alternating the
+                                                    legs; each figure the median of three 20-step windows after 6 warm-up steps
+  python tools/c4_layout_ab.py --leg nhwc-hip       one leg alone, 6 + 30 steps: the program for `rocprofv3 --kernel-trace --stats -- ...`
+  python tools/c4_layout_ab.py --units              the fused unit alone per ResNet-18 (M, C) at N = 1024, NHWC against NCHW, event-timed
+                                                    calls (forward = statistics + apply, backward = sums + backward apply) and TB/s
+  python tools/c4_layout_ab.py --summarise T.csv    buckets and per-(kernel, grid) rows of a rocprofv3 *_kernel_trace.csv (no GPU)
+Every mode prints JSON lines; --out FILE also appends them there."""
+import argparse
+import csv
+import json
+import os
+import statistics
+import sys
+import types
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+LEGS = {"nchw": ("contiguous", "torch"), "nhwc-torch": ("channels_last", "torch"), "nhwc-hip": ("channels_last", "hip")}
+# ResNet-18's units at N = 1024 on 64 x 64 images: (name, N, C, H, W, units with / without a residual per view)
+UNIT_SHAPES = [("stem", 1024, 64, 32, 32), ("layer 1", 1024, 64, 16, 16), ("layer 2", 1024, 128, 8, 8), ("layer 3", 1024, 256, 4, 4),
+               ("layer 4", 1024, 512, 2, 2)]
+
+
+def emit(out, obj):
+    line = json.dumps(obj)
+    print(line, flush=True)
+    if out:
+        with open(out, "a") as fh:
+            fh.write(line + "\n")
+
+
+def make_leg(leg):
+    """bench.py's c4 step (conv_config_leg) with the model and the inputs in the leg's memory format."""
+    import torch
+    from cl_ica_amd import resnet, threedident as T
+    from cl_ica_amd.optim import Adam
+    fmt_name, nhwc_mode = LEGS[leg]
+    fmt = getattr(torch, fmt_name + "_format" if fmt_name == "contiguous" else fmt_name)
+    dev = torch.device("cuda")
+    torch.manual_seed(0)
+    a = types.SimpleNamespace(position_only=True, rotation_and_color_only=False, rotation_only=False, color_only=False,
+                              non_periodic_rotation_and_color=False, box_constraint="fix", sphere_constraint=None,
+                              unsupervised_loss="l2", identity_solution=False, encoder="rn18")
+    f = T.setup_f(a, 3, 0).to(dev).to(memory_format=fmt)
+    f.train()
+    loss = T.make_unsupervised_loss(a, 3)
+    opt = Adam(f.parameters(), lr=1e-4)
+    x1 = torch.randn(1024, 3, 64, 64, device=dev)
+    x2 = (x1 + 0.1 * torch.randn_like(x1)).contiguous(memory_format=fmt)
+    x1 = x1.contiguous(memory_format=fmt)
+
+    def step():
+        resnet.NHWC_MODE = nhwc_mode            # (read at call time)
+        return T.train_step(((None, None), (x1, x2)), loss, opt, f, sync=False)[0]
+    return step
+
+
+def run_leg(leg, steps, warmup, windows):
+    import torch
+    step = make_leg(leg)
+    for _ in range(warmup):
+        last = step()
+    torch.cuda.synchronize()
+    ws = []
+    for _ in range(windows):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(steps):
+            last = step()
+        e1.record()
+        torch.cuda.synchronize()
+        ws.append(e0.elapsed_time(e1) * 1e-3)
+    el = statistics.median(ws)
+    res = {"leg": leg, "steps_per_s": round(steps / el, 2), "ms_per_step": round(1e3 * el / steps, 2), "final_loss": round(float(last.item()), 5),
+           "windows_s": [round(w, 4) for w in ws]}
+    del step
+    torch.cuda.empty_cache()
+    return res
+
+
+def units(out, reps=20):
+    """The unit alone at ResNet-18's shapes.  E = N C H W x 4 bytes; algorithmic bytes: forward E (statistics) + 2 E (apply), + E with a
+    residual; backward 3 E (sums) + 4 E (backward apply), + E with dr."""
+    import torch
+    from cl_ica_amd import ops
+    dev = torch.device("cuda")
+    for name, N, C, H, W in UNIT_SHAPES:
+        E = N * C * H * W * 4
+        w = torch.ones(C, device=dev); b = torch.zeros(C, device=dev)
+        for layout in ("nchw", "nhwc"):
+            fmt = torch.channels_last if layout == "nhwc" else torch.contiguous_format
+            x, r, dy = (torch.randn(N, C, H, W, device=dev).contiguous(memory_format=fmt) for _ in range(3))
+            fwd = ops.batchnorm2d_act_fwd_nhwc if layout == "nhwc" else ops.batchnorm2d_act_fwd
+            bwd = ops.batchnorm2d_act_bwd_nhwc if layout == "nhwc" else ops.batchnorm2d_act_bwd
+            ev = ops.batchnorm2d_act_eval_nhwc if layout == "nhwc" else ops.batchnorm2d_act_eval
+            for res in (False, True):
+                rr = r if res else None
+                y, m, i = fwd(x, w, b, None, None, 1e-5, 0.1, 0.0, residual=rr)
+                calls = {"forward (statistics + apply)": (lambda: fwd(x, w, b, None, None, 1e-5, 0.1, 0.0, residual=rr), (4 if res else 3) * E),
+                         "backward (sums + backward apply)": (lambda: bwd(x, y, dy, w, m, i, 0.0, need_dr=res), (8 if res else 7) * E),
+                         "inference apply": (lambda: ev(x, w, b, m, i.reciprocal().square(), 1e-5, 0.0, residual=rr), (3 if res else 2) * E)}
+                for what, (call, nbytes) in calls.items():
+                    for _ in range(3):
+                        call()
+                    torch.cuda.synchronize()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(reps):
+                        call()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    us = e0.elapsed_time(e1) * 1e3 / reps
+                    emit(out, {"unit": name, "M": N * H * W, "C": C, "E_MB": round(E / 1e6, 1), "layout": layout, "residual": res, "call": what,
+                               "us_per_call": round(us, 1), "TB_per_s": round(nbytes / us / 1e6, 2)})
+            del x, r, dy, y
+            torch.cuda.empty_cache()
+
+
+def bucket_of(name):
+    n = name
+    if "clica::bn2d::nhwc::avgpool" in n or "clica::avgpool" in n or "clica::bn2d::pool_" in n:
+        return "clica pool kernels"
+    if "clica::bn2d::nhwc" in n:
+        return "clica::bn2d::nhwc::* units"
+    if "clica::bn2d" in n:
+        return "clica::bn2d::* (NCHW)"
+    if "clica::" in n:
+        return "other HIP library kernels (head, loss, Adam)"
+    low = n.lower()
+    if "transpose" in low or "subtensorop" in low:
+        return "MIOpen layout transposes / SubTensorOp"
+    if "max_pool" in low or "maxpool" in low:
+        return "ATen max-pool (stem, unfused in NHWC)"
+    if "batch_norm" in low or "batchnorm" in low or "bn_fwd" in low or "bn_bwd" in low or "bnfwd" in low or "bnbwd" in low:
+        return "MIOpen / ATen BatchNorm"
+    if "at::native" in n or "at::" in n:
+        return "ATen element-wise / reductions / copies"
+    return "MIOpen / rocBLAS convolution kernels"
+
+
+def summarise(path, out, top=45):
+    rows = list(csv.DictReader(open(path)))
+    name_key = "Kernel_Name" if "Kernel_Name" in rows[0] else "Name"
+    gx = [k for k in ("Grid_Size_X", "Grid_Size") if k in rows[0]]
+    gy = "Grid_Size_Y" if "Grid_Size_Y" in rows[0] else None
+    wx = "Workgroup_Size_X" if "Workgroup_Size_X" in rows[0] else ("Workgroup_Size" if "Workgroup_Size" in rows[0] else None)
+    buckets, groups = {}, {}
+    total = 0.0
+    for r in rows:
+        d = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3      # us
+        total += d
+        full = r[name_key]
+        b = buckets.setdefault(bucket_of(full), [0.0, 0])
+        b[0] += d; b[1] += 1
+        short = full.replace("void ", "").replace("(anonymous namespace)::", "").split("(")[0][:96]
+        grid = (int(r[gx[0]]) // max(int(r[wx]), 1) if gx and wx else 0, int(r[gy]) if gy else 0)
+        groups.setdefault((short, grid), []).append(d)
+    emit(out, {"trace": path, "kernel_ms": round(total / 1e3, 1), "launches": len(rows)})
+    for k, (t, n) in sorted(buckets.items(), key=lambda kv: -kv[1][0]):
+        emit(out, {"bucket": k, "share_pct": round(100 * t / total, 1), "ms": round(t / 1e3, 1), "launches": n})
+    listed = sorted(groups.items(), key=lambda kv: -sum(kv[1]))[:top]
+    for (short, grid), ds in listed:
+        ds = sorted(ds)
+        # one (kernel, grid) may serve two tensor sizes (the C = 64 units of the stem and of layer 1): split at the widest gap over 2 x
+        cut = max(range(1, len(ds)), key=lambda i: ds[i] / max(ds[i - 1], 1e-9), default=None)
+        parts = [ds[:cut], ds[cut:]] if cut and ds[cut] > 2.0 * ds[cut - 1] else [ds]
+        for p in parts:
+            emit(out, {"kernel": short, "grid_workgroups": list(grid), "calls": len(p), "mean_us": round(statistics.fmean(p), 1),
+                       "min_us": round(p[0], 1), "max_us": round(p[-1], 1), "total_ms": round(sum(p) / 1e3, 2)})
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--leg", choices=sorted(LEGS), help="run this leg alone (for a profiler)")
+    ap.add_argument("--units", action="store_true")
+    ap.add_argument("--summarise", metavar="KERNEL_TRACE_CSV")
+    ap.add_argument("--steps", type=int, default=None)
+    ap.add_argument("--warmup", type=int, default=6)
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if args.summarise:
+        return summarise(args.summarise, args.out)
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("c4_layout_ab.py measures on the GPU: none here")
+    if args.units:
+        return units(args.out)
+    if args.leg:
+        return emit(args.out, dict(run_leg(args.leg, args.steps or 30, args.warmup, 1), run="alone"))
+    for leg in LEGS:                                   # MIOpen's find step of every leg, outside every window
+        emit(args.out, dict(run_leg(leg, 4, 2, 1), run="throw-away"))
+    for rnd in range(1, args.rounds + 1):
+        for leg in LEGS:
+            emit(args.out, dict(run_leg(leg, args.steps or 20, args.warmup, 3), run=f"round {rnd}"))
+
+
+if __name__ == "__main__":
+    main()
