@@ -23,6 +23,9 @@ same units on the kernels of csrc/bn2d_nhwc.hip, whose outputs and gradients are
 MIOpen's convolutions; the average pool follows under POOL_MODE "hip".  A residual in the other layout runs torch's path (no hidden
 copy), and the stem's max-pool is the unit followed by ``nn.MaxPool2d`` (the fused stem kernel holds NCHW planes in LDS).  The default
 is "torch": channels-last inputs run the modules' own forward, as they always did.
+
+Both layouts share the code here: ``_layout(x)`` names the layout once per unit, and ``_unit``, ``_BN2dActFn`` and ``_GlobalAvgPoolFn``
+take it as an argument that picks the ``ops`` function (``name`` or ``name_nhwc``) and the memory format of the incoming gradient.
 """
 from __future__ import annotations
 
@@ -54,47 +57,35 @@ if NHWC_MODE not in ("hip", "torch"):
     raise ValueError(f"CLICA_RESNET_NHWC={NHWC_MODE!r} (one of 'hip', 'torch')")
 
 _NHWC = torch.channels_last
+# A layout ("nchw" / "nhwc", what _layout gives) picks the memory format of a gradient and the ops function of a name, looked up on the
+# module at call time.
+_FORMAT = {"nchw": torch.contiguous_format, "nhwc": _NHWC}
+
+
+def _op(name, layout):
+    return getattr(ops, name if layout == "nchw" else name + "_nhwc")
 
 
 class _BN2dActFn(torch.autograd.Function):
-    """nn.BatchNorm2d in training mode + the shortcut add + the ReLU behind it (slope = 1: none) on clica_bn2d_act_fwd_train / _bwd.
-    `mod` is the module itself: its running statistics are updated in place by the forward's second launch, as its own forward does."""
+    """nn.BatchNorm2d in training mode + the shortcut add + the ReLU behind it (slope = 1: none) on clica_bn2d_act_fwd_train / _bwd or,
+    for `layout` "nhwc" (dense channels-last x and r; output and input gradients channels-last again), on clica_bn2d_nhwc_act_fwd_train /
+    _bwd.  `mod` is the module itself: its running statistics are updated in place by the forward's second launch, as its own forward does."""
 
     @staticmethod
-    def forward(ctx, x, r, weight, bias, mod, slope):
-        y, save_mean, save_invstd = ops.batchnorm2d_act_fwd(x, weight, bias, mod.running_mean, mod.running_var, mod.eps, mod.momentum, slope,
-                                                            residual=r)
+    def forward(ctx, x, r, weight, bias, mod, slope, layout):
+        y, save_mean, save_invstd = _op("batchnorm2d_act_fwd", layout)(x, weight, bias, mod.running_mean, mod.running_var, mod.eps,
+                                                                       mod.momentum, slope, residual=r)
         ctx.save_for_backward(x, y, weight, save_mean, save_invstd)
-        ctx.slope = slope
+        ctx.slope, ctx.layout = slope, layout
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
         x, y, weight, save_mean, save_invstd = ctx.saved_tensors
-        dx, dr, dw, db = ops.batchnorm2d_act_bwd(x, y, gy.contiguous(), weight, save_mean, save_invstd, ctx.slope,
-                                                 need_dr=ctx.needs_input_grad[1])
-        return dx, dr, dw, db, None, None
-
-
-class _BN2dActNhwcFn(torch.autograd.Function):
-    """_BN2dActFn on dense channels-last x (and r): clica_bn2d_nhwc_act_fwd_train / _bwd.  Output and input gradients are channels-last."""
-
-    @staticmethod
-    def forward(ctx, x, r, weight, bias, mod, slope):
-        y, save_mean, save_invstd = ops.batchnorm2d_act_fwd_nhwc(x, weight, bias, mod.running_mean, mod.running_var, mod.eps, mod.momentum,
-                                                                 slope, residual=r)
-        ctx.save_for_backward(x, y, weight, save_mean, save_invstd)
-        ctx.slope = slope
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gy):
-        x, y, weight, save_mean, save_invstd = ctx.saved_tensors
-        dx, dr, dw, db = ops.batchnorm2d_act_bwd_nhwc(x, y, gy.contiguous(memory_format=_NHWC), weight, save_mean, save_invstd, ctx.slope,
-                                                      need_dr=ctx.needs_input_grad[1])
-        return dx, dr, dw, db, None, None
+        dx, dr, dw, db = _op("batchnorm2d_act_bwd", ctx.layout)(x, y, gy.contiguous(memory_format=_FORMAT[ctx.layout]), weight, save_mean,
+                                                                save_invstd, ctx.slope, need_dr=ctx.needs_input_grad[1])
+        return dx, dr, dw, db, None, None, None
 
 
 class _BN2dActPoolFn(torch.autograd.Function):
@@ -118,31 +109,18 @@ class _BN2dActPoolFn(torch.autograd.Function):
 
 
 class _GlobalAvgPoolFn(torch.autograd.Function):
-    """flatten(nn.AdaptiveAvgPool2d(1)(x), 1) on clica_avgpool2d_global_fwd / _bwd."""
+    """flatten(nn.AdaptiveAvgPool2d(1)(x), 1) on clica_avgpool2d_global_fwd / _bwd or, for `layout` "nhwc" (a dense channels-last x), on
+    clica_avgpool2d_global_nhwc_fwd / _bwd.  The output and its gradient are matrices in both."""
 
     @staticmethod
-    def forward(ctx, x):
-        ctx.hw = (x.shape[2], x.shape[3])
-        return ops.avgpool2d_global_fwd(x)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gy):
-        return ops.avgpool2d_global_bwd(gy.contiguous(), *ctx.hw)
-
-
-class _GlobalAvgPoolNhwcFn(torch.autograd.Function):
-    """_GlobalAvgPoolFn on a dense channels-last x: clica_avgpool2d_global_nhwc_fwd / _bwd."""
-
-    @staticmethod
-    def forward(ctx, x):
-        ctx.hw = (x.shape[2], x.shape[3])
-        return ops.avgpool2d_global_fwd_nhwc(x)
+    def forward(ctx, x, layout):
+        ctx.hw, ctx.layout = (x.shape[2], x.shape[3]), layout
+        return _op("avgpool2d_global_fwd", layout)(x)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        return ops.avgpool2d_global_bwd_nhwc(gy.contiguous(), *ctx.hw)
+        return _op("avgpool2d_global_bwd", ctx.layout)(gy.contiguous(), *ctx.hw), None
 
 
 def _layout(x):
@@ -159,11 +137,12 @@ def _same_layout(r, layout) -> bool:
     return r.is_contiguous() if layout == "nchw" else r.is_contiguous(memory_format=_NHWC)
 
 
-def _bn2d_on_hip(m, x, r=None) -> bool:
-    """Do the bn2d kernels cover this module on this input (and residual)?  Anything else runs the module's own forward, as before."""
-    if NORM_MODE != "hip" or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or _layout(x) is None:
+def _bn2d_on_hip(m, x, layout, r=None) -> bool:
+    """Do the bn2d kernels cover this module on this input of `layout` (= _layout(x)) and residual?  Anything else runs the module's own
+    forward, as before."""
+    if NORM_MODE != "hip" or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or layout is None:
         return False
-    if r is not None and not (r.is_cuda and r.dtype == torch.float32 and r.shape == x.shape and _same_layout(r, _layout(x))):
+    if r is not None and not (r.is_cuda and r.dtype == torch.float32 and r.shape == x.shape and _same_layout(r, layout)):
         return False
     if not (isinstance(m, nn.BatchNorm2d) and m.affine and m.track_running_stats and m.momentum is not None and x.shape[1] == m.num_features):
         return False
@@ -177,28 +156,27 @@ def _bn2d_on_hip(m, x, r=None) -> bool:
 
 def _unit(bn, relu, x, r=None):
     """relu(bn(x) + r) -- `relu` None: no activation, `r` None: no shortcut -- as one fused call where the kernels apply."""
-    if not _bn2d_on_hip(bn, x, r):
+    layout = _layout(x)
+    if not _bn2d_on_hip(bn, x, layout, r):
         y = bn(x)
         if r is not None:
             y = y + r
         return y if relu is None else relu(y)
     slope = 1.0 if relu is None else 0.0
-    if _layout(x) == "nhwc":
-        if bn.training:
-            ops.bn2d_nhwc_workspace(x.shape[0] * x.shape[2] * x.shape[3], x.shape[1], x.device)     # (raises while capturing without a warm-up)
-            bn.num_batches_tracked.add_(1)
-            return _BN2dActNhwcFn.apply(x, r, bn.weight, bn.bias, bn, slope)
-        return ops.batchnorm2d_act_eval_nhwc(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.eps), slope, residual=r)
     if bn.training:
-        ops.bn2d_workspace(x.shape[0], x.shape[1], x.shape[2] * x.shape[3], x.device)   # (raises while capturing without a warm-up: before anything is counted)
+        N, C, H, W = x.shape
+        if layout == "nchw":                                # (raises while capturing without a warm-up: before anything is counted)
+            ops.bn2d_workspace(N, C, H * W, x.device)
+        else:
+            ops.bn2d_nhwc_workspace(N * H * W, C, x.device)
         bn.num_batches_tracked.add_(1)                      # in place on the device: capturable
-        return _BN2dActFn.apply(x, r, bn.weight, bn.bias, bn, slope)
-    return ops.batchnorm2d_act_eval(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.eps), slope, residual=r)
+        return _BN2dActFn.apply(x, r, bn.weight, bn.bias, bn, slope, layout)
+    return _op("batchnorm2d_act_eval", layout)(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.eps), slope, residual=r)
 
 
 def _stem_pool_on_hip(bn, pool, x) -> bool:
     """Does the fused stem unit cover bn + relu + `pool` on this input?  Otherwise: the unfused unit, then the module."""
-    if POOL_MODE != "hip" or not _bn2d_on_hip(bn, x) or _layout(x) != "nchw":      # (the fused stem kernel holds NCHW planes in LDS)
+    if POOL_MODE != "hip" or _layout(x) != "nchw" or not _bn2d_on_hip(bn, x, "nchw"):      # (the fused stem kernel holds NCHW planes in LDS)
         return False
     one = lambda v, k: v == k or v == (k, k)
     if not (type(pool) is nn.MaxPool2d and one(pool.kernel_size, 3) and one(pool.stride, 2) and one(pool.padding, 1) and one(pool.dilation, 1)
@@ -277,7 +255,7 @@ class ResNet18(nn.Module):
             x = _stem(self.bn1, self.relu, self.maxpool, self.conv1(x))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         if _avgpool_on_hip(self.avgpool, x):
-            return self.fc((_GlobalAvgPoolNhwcFn if _layout(x) == "nhwc" else _GlobalAvgPoolFn).apply(x))
+            return self.fc(_GlobalAvgPoolFn.apply(x, _layout(x)))
         return self.fc(torch.flatten(self.avgpool(x), 1))
 
 

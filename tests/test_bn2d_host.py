@@ -119,6 +119,27 @@ def test_ops_wrappers_refuse_other_inputs():
         ops.batchnorm2d_act_eval(x[:, :, :, :1], w, b, b, w)
     with pytest.raises(ValueError, match="contiguous NCHW"):
         ops.batchnorm2d_act_bwd(x.permute(0, 1, 3, 2), x, x, w, b, w)
+    # maps, then vectors, then devices, in both layouts: what the channels-last functions refuse on CPU tensors, these refuse alike
+    cl = x.contiguous(memory_format=torch.channels_last)
+    assert not cl.is_contiguous()
+    with pytest.raises(ValueError, match="shape of x"):
+        ops.batchnorm2d_act_fwd(x, w, b, residual=torch.randn(4, 8, 4, 1))
+    with pytest.raises(ValueError, match="contiguous NCHW"):
+        ops.batchnorm2d_act_fwd(x, w, b, residual=cl)                       # layout mismatch of the residual
+    with pytest.raises(ValueError, match="contiguous NCHW"):
+        ops.batchnorm2d_act_bwd(x, cl, x, w, b, w)                          # y
+    with pytest.raises(ValueError, match="shape of x"):
+        ops.batchnorm2d_act_bwd(x, x, x[:2], w, b, w)                       # dy
+    with pytest.raises(ValueError, match="contiguous values"):
+        ops.batchnorm2d_act_fwd(x, w[:3], b)
+    with pytest.raises(ValueError, match="contiguous values"):
+        ops.batchnorm2d_act_fwd(x, w, torch.zeros(16)[::2])
+    with pytest.raises(ValueError, match="come together"):
+        ops.batchnorm2d_act_fwd(x, w, b, running_mean=b)
+    with pytest.raises(ValueError, match="contiguous values"):
+        ops.batchnorm2d_act_eval(x, w, b, b[:7], w)
+    with pytest.raises(ValueError, match="contiguous matrix"):
+        ops.avgpool2d_global_bwd(torch.randn(4, 8).t(), 2, 2)
 
 
 def test_state_dict_keys_are_unchanged():

@@ -9,33 +9,10 @@ import pytest
 import torch
 
 import bn2d_oracle as B
+from bn_family_util import bits, deterministic_convolutions, dev, host, off_by_4_bytes, raw, refuse  # noqa: F401 (the autouse fixture)
 from conftest import PARITY
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(autouse=True)
-def deterministic_convolutions(monkeypatch):
-    """MIOpen's default choice of convolution kernels is not reproducible run to run (split-K weight gradients with atomics: two "torch"-mode
-    passes of the backbone differ in every tensor); the tests here that compare bits across passes are about the bn2d units, so the
-    convolutions between them run in torch's deterministic mode."""
-    monkeypatch.setattr(torch.backends.cudnn, "deterministic", True)
-
-
-def dev(a):
-    return torch.tensor(np.ascontiguousarray(a), dtype=torch.float32).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def bits(t):
-    return host(t).view(np.uint32)
-
-
-def raw(t):
-    return np.ascontiguousarray(host(t)).reshape(-1).view(np.uint8)
 
 
 def maps(c, shape):
@@ -95,15 +72,6 @@ def test_eval_abi_against_the_oracle(shape):
                 y = ops.batchnorm2d_act_eval(x, dev(c["gamma"]), dev(c["beta"]), dev(rm), dev(rv), B.EPS, slope, residual=r)
                 PARITY.check("bn2d_abi", f"eval {N}x{C}x{H}x{W} cls{cls} slope{slope} res{int(residual)}", "y", B.to_rows(host(y)),
                              B.evaluate(c, rm, rv, slope))
-
-
-def off_by_4_bytes(t):
-    """A contiguous copy of t whose storage starts 4 bytes off a 16-byte boundary."""
-    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
-    u = buf[1:].view(t.shape)
-    u.copy_(t)
-    assert u.is_contiguous() and u.data_ptr() % 16 == 4
-    return u
 
 
 @pytest.mark.parametrize("shape", B.UNALIGNED_SHAPES, ids=lambda s: "x".join(map(str, s)))
@@ -245,10 +213,6 @@ def test_backbone_train_step_moves_every_parameter_by_at_most_lr(monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------ 4. the HIP path is really taken
-def refuse(*a, **k):
-    raise AssertionError("torch's own normalisation or activation kernel was called")
-
-
 def test_the_hip_path_is_taken(monkeypatch):
     from cl_ica_amd import resnet
     f, x = backbone()

@@ -11,33 +11,11 @@ import torch
 
 import bn2d_nhwc_cases as K
 import bn2d_oracle as B
+from bn_family_util import bits, deterministic_convolutions, dev, host, raw, refuse  # noqa: F401 (the autouse fixture)
 from conftest import PARITY
 
 pytestmark = pytest.mark.gpu
 CL = torch.channels_last
-
-
-@pytest.fixture(autouse=True)
-def deterministic_convolutions(monkeypatch):
-    """As in tests/test_gpu_bn2d.py: the tests that compare bits across passes are about the units, so the convolutions between them run
-    in torch's deterministic mode."""
-    monkeypatch.setattr(torch.backends.cudnn, "deterministic", True)
-
-
-def dev(a):
-    return torch.tensor(np.ascontiguousarray(a), dtype=torch.float32).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def bits(t):
-    return host(t).view(np.uint32)
-
-
-def raw(t):
-    return np.ascontiguousarray(host(t)).reshape(-1).view(np.uint8)
 
 
 def nhwc(rows, shape):
@@ -324,10 +302,6 @@ def spy_on(monkeypatch):
     return calls
 
 
-def refuse(*a, **k):
-    raise AssertionError("torch's own normalisation or activation kernel was called")
-
-
 def test_the_nhwc_path_is_taken(monkeypatch):
     from cl_ica_amd import resnet
     f, x = backbone()
@@ -491,6 +465,6 @@ def test_average_pool_against_fp64(shape):
     # through autograd, as resnet.py calls it
     from cl_ica_amd import resnet
     xin = x.cuda().requires_grad_(True)
-    out = resnet._GlobalAvgPoolNhwcFn.apply(xin)
+    out = resnet._GlobalAvgPoolFn.apply(xin, "nhwc")
     (out * dy.cuda()).sum().backward()
     assert np.array_equal(bits(out), bits(y)) and np.array_equal(raw(xin.grad), raw(dx)) and dense_cl(xin.grad)

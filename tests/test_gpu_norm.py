@@ -10,25 +10,10 @@ import pytest
 import torch
 
 import norm_oracle as O
+from bn_family_util import bits, dev, host, raw
 from conftest import PARITY, fill_formula
 
 pytestmark = pytest.mark.gpu
-
-
-def dev(a):
-    return torch.tensor(np.ascontiguousarray(a), dtype=torch.float32).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def bits(t):
-    return host(t).view(np.uint32)
-
-
-def raw(t):
-    return np.ascontiguousarray(host(t)).reshape(-1).view(np.uint8)
 
 
 # ------------------------------------------------------------------------------------------------ 1. ABI sweep against the oracle

@@ -9,34 +9,12 @@ import pytest
 import torch
 
 import pool2d_oracle as Q
+from bn_family_util import bits, deterministic_convolutions, dev, host, off_by_4_bytes, raw  # noqa: F401 (the autouse fixture)
 from conftest import PARITY
 
 pytestmark = pytest.mark.gpu
 F = torch.nn.functional
 ids = lambda s: "x".join(map(str, s))
-
-
-@pytest.fixture(autouse=True)
-def deterministic_convolutions(monkeypatch):
-    """As in tests/test_gpu_bn2d.py: MIOpen's default convolution kernels are not reproducible run to run; the tests here that compare
-    bits across passes are about the pools, so the convolutions run in torch's deterministic mode."""
-    monkeypatch.setattr(torch.backends.cudnn, "deterministic", True)
-
-
-def dev(a):
-    return torch.tensor(np.ascontiguousarray(a), dtype=torch.float32).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def bits(t):
-    return host(t).view(np.uint32)
-
-
-def raw(t):
-    return np.ascontiguousarray(host(t)).reshape(-1).view(np.uint8)
 
 
 def same_bits(a, b):
@@ -136,15 +114,6 @@ def test_eval_abi_against_the_oracle(shape):
             PARITY.check("pool2d_abi", f"eval {N}x{C}x{H}x{W} cls{cls} slope{slope}", "p", host(p), Q.evaluate(c, shape, rm, rv, slope))
             y = ops.batchnorm2d_act_eval(x, gamma, beta, dev(rm), dev(rv), Q.EPS, slope)
             assert same_bits(p, F.max_pool2d(y, 3, 2, 1))
-
-
-def off_by_4_bytes(t):
-    """A contiguous copy of t whose storage starts 4 bytes off a 16-byte boundary."""
-    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
-    u = buf[1:].view(t.shape)
-    u.copy_(t)
-    assert u.is_contiguous() and u.data_ptr() % 16 == 4
-    return u
 
 
 @pytest.mark.parametrize("shape", Q.UNALIGNED_SHAPES, ids=ids)

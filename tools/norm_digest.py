@@ -16,21 +16,10 @@ import torch                                                  # noqa: E402
 import norm_oracle as O                                       # noqa: E402
 import bn2d_oracle as B                                       # noqa: E402
 import pool2d_oracle as Q                                     # noqa: E402
+from bn_family_util import dev, off_by_4_bytes                # noqa: E402
 from cl_ica_amd import ops                                    # noqa: E402
 
 WORKLOAD = [(1024, 64, 32, 32), (1024, 64, 16, 16), (1024, 128, 8, 8), (1024, 256, 4, 4), (1024, 512, 2, 2)]
-
-
-def dev(a):
-    return None if a is None else torch.tensor(np.ascontiguousarray(a), dtype=torch.float32).cuda()
-
-
-def off_by_4_bytes(t):
-    """A contiguous copy of t whose storage starts 4 bytes off a 16-byte boundary."""
-    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
-    u = buf[1:].view(t.shape)
-    u.copy_(t)
-    return u
 
 
 def eval_stats(c):
