@@ -98,11 +98,84 @@ class StepPlan:
     wgrad_halves: bool         # data parallel: the grouped weight gradients go out in two halves
 
 
+@dataclass(frozen=True)
+class EncoderPlan:
+    """Which encoder pipeline a trainer runs, decided once by plan_encoder() from host facts; the trainer's flags of the same names are
+    copies of these fields, and nothing assigns them afterwards."""
+    path: str                  # "whole-stack": one launch for the stack (widths <= 512, <= 8 layers) | "per-layer": one GEMM per layer
+    arith: str                 # "native_fp32" | "bf16x3" | "f16x2": what the matrix cores multiply (per-layer: in the split layers only)
+    fused_forward: bool        # the forward is the whole-stack launch (= path "whole-stack")
+    fused_backward: bool       # ... and so are the data-gradient chain and the grouped weight gradients (more than one Linear; a
+                               #     single-Linear encoder runs its backward through the per-layer body)
+    mix_in_forward: bool       # the mixing net g runs in the whole-stack forward's prologue
+    split_bf16: bool           # whole-stack forward and chain in a split arithmetic (bf16x3, or f16x2 with split_f16)
+    split_f16: bool            # ... in f16x2
+    split_wgrad: bool          # ... and the grouped weight gradients of the MFMA-sized layers on plane copies
+    split_wgrad_wide: bool     # per-layer path: the weight gradients of the MFMA-sized layers on plane copies
+    split_f16_wide: bool       # ... in f16x2
+    kinds: tuple               # mlp_wgrad_split_kind per layer, whole-stack family (() unless split_bf16)
+    wide_kinds: tuple          # ... per-layer family (() unless split_wgrad_wide)
+    chain: frozenset           # per-layer path: the layers whose forward and data gradient run on the split GEMMs as well
+    chain_min: int             # ... the least width, on both sides, that puts a layer there (0: no split weight gradients)
+    acts_planes_only: tuple    # per layer: the forward writes this activation as planes only (acts_out[l] is None)
+    dz_planes_only: tuple      # per chain link (fused_backward): dZ_l is written as planes only (dz_out[l] is None)
+
+    def __post_init__(self):
+        assert self.fused_forward == (self.path == "whole-stack") and (self.fused_forward or not self.fused_backward)
+        assert self.fused_backward or not (self.split_bf16 or self.split_wgrad), "the split whole-stack kernels need the fused backward"
+        assert self.split_bf16 or not (self.split_f16 or self.split_wgrad)
+        assert not (self.fused_forward and self.split_wgrad_wide) and (self.split_wgrad_wide or not (self.split_f16_wide or self.chain))
+        assert self.arith == ("f16x2" if self.split_f16 or self.split_f16_wide else
+                              "bf16x3" if self.split_bf16 or self.split_wgrad_wide else "native_fp32")
+
+
+def plan_encoder(shapes, slope: float, gpu: bool, fused_forward: bool, want_split: bool, arith_f16: bool, keep_fp32_copies: bool = False,
+                 mix_ok: bool = True) -> EncoderPlan:
+    """The encoder path of a Linear / LeakyReLU stack with weight shapes `shapes` = [(out, in), ...]: host logic over the library's host
+    planners, no launch, no allocation.  `want_split` / `arith_f16`: the resolved split_bf16 / split_arith requests (environment
+    included); `mix_ok`: the mixing net is one the whole-stack prologue can run."""
+    L = len(shapes)
+    widths = [s[0] for s in shapes]
+    fused_fwd = bool(fused_forward) and ops.mlp_fwd_fusable([torch.empty(s, device="meta") for s in shapes])
+    fused_bwd = fused_fwd and L > 1
+    # whole-stack kernels and weight gradients on the bf16 matrix cores with exact 3-way bf16 operand splits (fp32 emulation: six bf16
+    # products per fp32 product, fp32 accumulate, fp32-grade error; DESIGN 4.1d) -- the default where the encoder fits them
+    split = fused_bwd and want_split and sum((w + 31) // 32 * 32 for w in widths) <= 3456       # on-chip bias table (fused_mlp.hip)
+    # f16x2: two fp16 pieces per operand with per-tensor power-of-two scales, three MFMA products (half the matrix work, 4 B/element;
+    # include/clica.h "f16x2 arithmetic"); bf16x3 (full fp32 exponent range) stays for a slope outside (0, 1) and off the GPU
+    f16 = bool(arith_f16 and 0.0 < slope < 1.0 and gpu)
+    # split weight gradients (csrc/wgrad_split.hip): the MFMA-sized layers read BOTH operands as planes that the split forward /
+    # backward-chain kernels write instead of the fp32 copies (nobody else reads a hidden activation or dZ); the tiny first / last
+    # layer keeps the fp32 VALU kernel, so the tensors next to them stay fp32 as well
+    kinds = tuple(ops.mlp_wgrad_split_kind(*s) for s in shapes) if split else ()
+    split_wgrad = bool(split and L >= 3 and kinds[0] == 1 and kinds[-1] == 1)
+    only = split_wgrad and not keep_fp32_copies
+    # Per-layer path (a width beyond 512, BASELINE config 3): forward and data gradients on the fp32-MFMA kernels, the WEIGHT gradients
+    # of the MFMA-sized layers in the split arithmetic on plane copies that an HBM-bound conversion kernel makes of the fp32
+    # activations / gradients (clica_mlp_planes_from_f32); f16x2 keeps its per-tensor scales in the Split16 state (at most 8 layers)
+    wide = bool(want_split and not fused_fwd)
+    f16_wide = wide and f16 and L <= 8
+    wide_kinds = tuple(ops.mlp_wgrad_split_kind(*s) for s in shapes) if wide else ()
+    # ... and, for the layers that are wide on BOTH sides (config 3's three 2000 x 2000 layers), forward and data gradient too: split
+    # GEMMs with fused epilogues on T-plane operands (csrc/wgrad_split.hip: gemm_split_k; 1.7x the fp32-MFMA kernels at
+    # 12288 x 2000 x 2000).  bf16x3: from 1024 -- with the 400-wide layers in the chain one p = 1 gradient check of G13 measures 1.1e-5;
+    # f16x2: from 384 -- all of config 3's checks hold 1e-5 and the step gains 13 %: 198 -> 225 steps/s
+    cmin = (384 if f16_wide else 1024) if wide else 0
+    chain = frozenset(l for l in range(1, L - 1) if wide and wide_kinds[l] == 0 and min(shapes[l]) >= cmin)
+    return EncoderPlan(path="whole-stack" if fused_fwd else "per-layer",
+                       arith="f16x2" if f16 and (split or f16_wide) else "bf16x3" if split or wide else "native_fp32",
+                       fused_forward=fused_fwd, fused_backward=fused_bwd, mix_in_forward=fused_fwd and mix_ok,
+                       split_bf16=bool(split), split_f16=bool(split and f16), split_wgrad=split_wgrad, split_wgrad_wide=wide,
+                       split_f16_wide=f16_wide, kinds=kinds, wide_kinds=wide_kinds, chain=chain, chain_min=cmin,
+                       acts_planes_only=tuple(only and l < L - 1 and kinds[l + 1] == 0 for l in range(L)),
+                       dz_planes_only=tuple(only and kinds[l] == 0 for l in range(L - 1)) if fused_bwd else ())
+
+
 class _FusedTrainer:
-    """What the contrastive and the supervised step share: the encoder paths, arenas, sampler and mixing net, pack, forward, heads,
-    backward chain, weight gradients, optimizer, calibration and guard bookkeeping of the f16x2 arithmetic, checkpoints, capture and
-    step / step_injected.  A subclass brings the objective: _enc_rows, _allocate_loss, loss_forward_backward, _objective_folds,
-    _result, inject, plan_summary and what its loss carries into a checkpoint."""
+    """What the contrastive and the supervised step share: the encoder paths (EncoderPlan: one forward and one backward body each),
+    arenas, sampler and mixing net, pack, forward, heads, backward chain, weight gradients, optimizer, calibration and guard bookkeeping
+    of the f16x2 arithmetic, checkpoints, capture and step / step_injected.  A subclass brings the objective: _enc_rows, _allocate_loss,
+    loss_forward_backward, _objective_folds, _result, inject, plan_summary and what its loss carries into a checkpoint."""
     p = tau = alpha = None           # (the contrastive objective's; checkpoints carry them as None otherwise)
     keep_fp32_copies = False         # (inspection, set on the class before construction: the split path also writes every fp32 copy)
 
@@ -159,61 +232,52 @@ class _FusedTrainer:
             if isinstance(m, (nn.modules.batchnorm._BatchNorm, nn.GroupNorm, nn.LayerNorm)):
                 raise ValueError(f"{type(self).__name__}: the encoder holds a normalisation module ({idx}: {m}); the fused step runs plain "
                                  "Linear / LeakyReLU stacks only -- train get_mlp(layer_normalization=...) through autograd")
+            if isinstance(m, nn.Linear) and m.bias is None:
+                raise ValueError(f"{type(self).__name__}: the encoder holds a Linear without bias ({idx}: {m}); every kernel of the fused "
+                                 "step computes a bias and its gradient")
         self.linears: List[nn.Linear] = [m for m in mods if isinstance(m, nn.Linear)]
         slopes = {m.negative_slope for m in mods if isinstance(m, nn.LeakyReLU)}
         self.slope = slopes.pop() if slopes else 0.01
         heads = [m for m in mods if isinstance(m, (ls.RescaleLayer, ls.SoftclipLayer))]
         self.head = heads[0] if heads else None
         self._flatten_parameters()
-        self.fused_forward = bool(fused_forward) and ops.mlp_fwd_fusable([lin.weight for lin in self.linears])
-        # mixing net g inside the fused forward's prologue (needs the one-launch forward, n <= 16)
-        self.mix_in_forward = self.fused_forward and self.n <= 16 and self.g_act_kind == 0
-        self._x_pending = False
-        self.packed = None
-        self.packed_t = None
-        self._packed_current = False
-        self.fused_backward = self.fused_forward and len(self.linears) > 1
-        # encoder arithmetic: the whole-stack kernels and the weight gradients on the bf16 matrix cores with exact 3-way bf16
-        # operand splits (fp32 emulation: six bf16 products per fp32 product, fp32 accumulate, fp32-grade error) --
-        # the default where the encoder fits the whole-stack kernels; split_bf16=False / CLICA_SPLIT_BF16=0 = native fp32 MFMA
+        # the encoder path (EncoderPlan).  split_bf16=False / CLICA_SPLIT_BF16=0: native fp32 MFMA; split_arith / CLICA_SPLIT_ARITH: "f16"
+        # (f16x2, the default) or "bf16" (the bf16x3 scheme: six products, 6 B/element, full fp32 exponent range)
         want_split = (os.environ.get("CLICA_SPLIT_BF16", "1") == "1") if split_bf16 is None else bool(split_bf16)
-        self._want_split = want_split
-        self.split_bf16 = self.fused_backward and want_split and all(lin.bias is not None for lin in self.linears) and \
-            sum((lin.out_features + 31) // 32 * 32 for lin in self.linears) <= 3456      # on-chip bias table (fused_mlp.hip)
-        # which split arithmetic (round 5): "f16" = two fp16 pieces per operand with per-tensor power-of-two scales, three MFMA products
-        # (half the matrix work, 4 B/element; include/clica.h "f16x2 arithmetic") -- the default; "bf16" = the round-3 bf16x3 scheme
-        # (six products, 6 B/element, full fp32 exponent range).  CLICA_SPLIT_ARITH / split_arith select; a slope outside (0, 1) keeps bf16.
         arith = (split_arith or os.environ.get("CLICA_SPLIT_ARITH", "f16")).lower()
         if arith not in ("f16", "bf16"):
             raise ValueError(f"split_arith must be 'f16' or 'bf16', got {arith!r}")
-        self._arith_f16 = bool(arith == "f16" and 0.0 < self.slope < 1.0 and self.device.type == "cuda")
-        self.split_f16 = bool(self.split_bf16 and self._arith_f16)          # whole-stack kernels in f16x2
-        self.split_f16_wide = False                                          # per-layer wide path in f16x2 (decided in _allocate)
-        self.s16 = None
-        self._s16_calibrated = False
+        # (the mixing net inside the whole-stack forward's prologue: n <= 16, LeakyReLU)
+        self.encoder_plan = ep = plan_encoder([tuple(lin.weight.shape) for lin in self.linears], self.slope, self.device.type == "cuda",
+                                              fused_forward, want_split, arith == "f16", keep_fp32_copies=bool(self.keep_fp32_copies),
+                                              mix_ok=self.n <= 16 and self.g_act_kind == 0)
+        for name in ("fused_forward", "fused_backward", "mix_in_forward", "split_bf16", "split_f16", "split_f16_wide", "split_wgrad",
+                     "split_wgrad_wide", "chain"):
+            setattr(self, name, getattr(ep, name))
+        self.grouped_wgrad = ep.fused_backward        # (one grouped launch for every layer's weight gradient: bench.py reads the name)
+        self.wide_kinds = list(ep.wide_kinds)
+        self.packed = self.packed_t = None
+        self._x_pending = self._packed_current = self._s16_calibrated = False
         if self.world > 1:
             # identical replicas by construction: rank 0's parameters and mixing weights win (callers that seed every rank
             # identically are unaffected; callers that do not would otherwise train `world` different models silently)
-            dist.broadcast(self.param_arena, src=dist.get_global_rank(process_group, 0) if process_group is not None else 0,
-                           group=process_group)
-            dist.broadcast(self.gW, src=dist.get_global_rank(process_group, 0) if process_group is not None else 0,
-                           group=process_group)
+            src = dist.get_global_rank(process_group, 0) if process_group is not None else 0
+            dist.broadcast(self.param_arena, src=src, group=process_group)
+            dist.broadcast(self.gW, src=src, group=process_group)
+        self.s16 = ops.Split16(len(self.linears), self.device) if ep.arith == "f16x2" else None
+        if self.s16 is not None and self.dp:      # all ranks must take the guard's decision together: the verdict is all-reduced with the gradients
+            self.s16.set_dp_poison(self._guard_slot)
         self._allocate()
-        if self.split_f16 or self.split_f16_wide:
-            self.s16 = ops.Split16(len(self.linears), self.device)
-            self._init_wide_ones()
-            if self.dp:      # all ranks must take the guard's decision together: the verdict is all-reduced with the gradients
-                self.s16.set_dp_poison(self._guard_slot)
-        self._watch_versions = True            # step(): parameters written from outside (load_state_dict, copy_) -> recalibrate the f16x2 scales
+        self._watch_versions = True           # step(): parameters written from outside (load_state_dict, copy_) -> recalibrate the f16x2 scales
         self._versions_seen = self._param_versions()
         self._guard_skipped_seen = 0
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         # data parallel + grouped weight gradients: the grouped launch is issued in TWO halves (layers L-1 .. h, then h-1 .. 0) and
         # the first half's slice of the gradient arena is all-reduced on the communication stream while the second half's GEMMs run
         L = len(self.linears)
-        self.wgrad_halves = bool(self.dp and self.fused_backward and self.grouped_wgrad and L >= 4)
+        self.wgrad_halves = bool(self.dp and self.fused_backward and L >= 4)
         self._half = L // 2
-        if self.wgrad_halves and self.group_ws is not None:
+        if self.wgrad_halves:
             # each half's launch plans its own contraction splits (fewer tiles -> more splits per layer -> larger slabs than in the
             # all-layer plan the workspace was sized for: 59.3 MB against 58.5 MB for the n = 10 stack at B = 6144)
             shapes = [tuple(lin.weight.shape) for lin in self.linears]
@@ -245,11 +309,11 @@ class _FusedTrainer:
         """Decided once, when everything the decisions depend on is constructed (StepPlan)."""
         # The optimizer can ride in the weight-gradient reduction when ONE whole-stack split launch produces every gradient of the
         # arena and nothing has to happen between gradient and update (no data-parallel all-reduce, no gradient scaling).
+        ep = self.encoder_plan
         lin_ids = {id(q) for lin in self.linears for q in (lin.weight, lin.bias)}
-        adam = bool(self.split_wgrad and self.fused_backward and self.grouped_wgrad and self.buckets is None
-                    and self.world * self.dry_ranks == 1 and all(lin.bias is not None for lin in self.linears)
+        adam = bool(ep.split_wgrad and self.buckets is None and self.world * self.dry_ranks == 1
                     and all(id(q) in lin_ids for q in self.f.parameters()))
-        tail = bool(adam and self.chain_tail and self.dz_out[0] is not None and
+        tail = bool(adam and self.chain_tail and not ep.dz_planes_only[0] and
                     ops.mlp_chain_tail_supported([tuple(lin.weight.shape) for lin in self.linears]))
         # the chain runs with its tail directly on dy: no pool beyond this rank's rows, no output head -- then it can finish dy itself
         on_dy = tail and not self.dp and self.emulate_pool <= 1 and self.head is None
@@ -303,87 +367,26 @@ class _FusedTrainer:
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
 
     def _allocate(self):
+        """What every path has (latents, encoder input, fp32 activations, output, head, objective), then the path's own buffers."""
         dev, B, n = self.device, self.B, self.n
         R = self._enc_rows()
         f32 = dict(dtype=torch.float32, device=dev)
         self.z = torch.empty((2 * B, n), **f32)        # rows [0,B): z ; [B,2B): z~  (the sampler draws the pair)
         self.x = torch.empty((R, n), **f32)            # g(z), g(z~): the encoder's input rows
-        widths = [lin.out_features for lin in self.linears]
-        self.acts = [torch.empty((R, w), **f32) for w in widths]     # post-activation outputs; last = pre-head
+        L = len(self.linears)
+        self.acts = [torch.empty((R, lin.out_features), **f32) for lin in self.linears]     # post-activation outputs; last = pre-head
         self.y = torch.empty((R, n), **f32) if self.head is not None else self.acts[-1]
         self.inv_norm = torch.empty((R,), **f32) if isinstance(self.head, ls.RescaleLayer) else None
-        wmax = max(widths + [n])
-        self.dbuf = [torch.empty((R, wmax), **f32) for _ in range(3)]
         self.side_stream = torch.cuda.Stream(device=dev) if (dev.type == "cuda" and self.overlap_backward) else None
         self._allocate_loss(R)
-        nb = C.c_size_t(); need = 0
-        for lin in self.linears:
-            _lib.check(_lib.load().clica_linear_wgrad_workspace_bytes(R, lin.out_features, lin.in_features, C.byref(nb)), "wgrad ws")
-            need = max(need, nb.value)
-        self.wgrad_ws = torch.zeros(need, dtype=torch.uint8, device=dev)
-        self.wgrad_ws2 = torch.zeros(need, dtype=torch.uint8, device=dev)    # second stream's slabs
-        self.dz = [torch.empty((R, w), **f32) for w in widths[:-1]] if self.fused_backward else None   # dZ_l for the wgrads
-        self.grouped_wgrad = self.fused_backward and all(lin.bias is not None for lin in self.linears)
-        self.group_ws = ops.mlp_wgrad_workspace(R, [tuple(lin.weight.shape) for lin in self.linears], dev) if self.grouped_wgrad else None
-        # sign bits of every hidden activation, written by the fused forward, read by the fused backward chain
-        self.signmasks = (ops.mlp_signmask_alloc(R, len(self.linears) - 1, dev) + [None]) if self.fused_backward else None
-        # split-bf16 weight gradients (csrc/wgrad_split.hip): the MFMA-sized layers read BOTH operands as bf16 planes that the
-        # split forward / backward-chain kernels write instead of the fp32 copies (nobody else reads a hidden activation or
-        # dZ); the tiny first / last layer keeps the fp32 VALU kernel, so the tensors next to them stay fp32 as well.
-        L = len(self.linears)
-        kinds = [ops.mlp_wgrad_split_kind(lin.out_features, lin.in_features) for lin in self.linears] if self.split_bf16 else []
-        self.split_wgrad = bool(self.split_bf16 and self.grouped_wgrad and L >= 3 and kinds[0] == 1 and kinds[-1] == 1)
-        self.act_planes = [None] * L
-        self.dz_planes = [None] * L
-        self.acts_out = list(self.acts)                      # what the forward writes as fp32 (None: planes only)
-        self.dz_out = list(self.dz) if self.dz is not None else None
-        if self.split_wgrad:
-            keep = bool(self.keep_fp32_copies)
-            for l in range(L):
-                if kinds[l] == 0:                            # dW_l = dZ_l^T acts_{l-1} on the bf16 / fp16 matrix cores
-                    self.act_planes[l - 1] = ops.mlp_planes_alloc(R, widths[l - 1], True, dev, f16=self.split_f16)
-                    self.dz_planes[l] = ops.mlp_planes_alloc(R, widths[l], False, dev, f16=self.split_f16)
-            for l in range(L - 1):
-                if not keep and kinds[l + 1] == 0:           # acts[l] feeds only an MFMA-sized weight gradient
-                    self.acts_out[l] = None
-                if not keep and kinds[l] == 0:
-                    self.dz_out[l] = None
-            self.group_ws = ops.mlp_wgrad_split_workspace(R, [tuple(lin.weight.shape) for lin in self.linears], dev)
-        # Wide encoders (a width beyond 512: the per-layer fp32 GEMM path, BASELINE config 3): forward and data gradients stay on
-        # the fp32-MFMA kernels, the WEIGHT gradients of the MFMA-sized layers run in the split-bf16 arithmetic on plane copies
-        # that an HBM-bound conversion kernel makes of the fp32 activations / gradients (clica_mlp_planes_from_f32)
-        self.split_wgrad_wide = bool(self._want_split and not self.fused_forward and not self.fused_backward
-                                     and all(lin.bias is not None for lin in self.linears))
-        self.wide_kinds = [ops.mlp_wgrad_split_kind(lin.out_features, lin.in_features) for lin in self.linears] if self.split_wgrad_wide else []
-        in_w = [lin.in_features for lin in self.linears]
-        if self.split_wgrad_wide:
-            # (round 5) the per-layer split kernels in the f16x2 arithmetic too: plane copies of 4 B/element, three products, per-tensor scales
-            # in the same Split16 state (tensor = (family, layer): activations by the layer they feed, gradients and weights by their layer)
-            self.split_f16_wide = f16w = bool(self._arith_f16 and L <= 8)
-            self.xin_planes = [ops.mlp_planes_alloc(R, in_w[l], True, dev, f16=f16w) if self.wide_kinds[l] == 0 else None for l in range(L)]
-            self.dzw_planes = [ops.mlp_planes_alloc(R, widths[l], False, dev, f16=f16w) if self.wide_kinds[l] == 0 else None for l in range(L)]
-            shapes = [tuple(lin.weight.shape) for lin in self.linears]
-            self.wide_ws = max((ops.mlp_wgrad_split_workspace(R, [shapes[l]], dev) for l in range(L) if self.wide_kinds[l] == 0),
-                               key=lambda t: t.numel(), default=None)
-        # ... and, for the layers that are wide on BOTH sides (>= 1024: config 3's three 2000 x 2000 layers), forward and data
-        # gradient too: split-bf16 GEMMs with fused epilogues on T-plane operands (csrc/wgrad_split.hip: gemm_split_k; 1.7x the
-        # fp32-MFMA kernels at 12288 x 2000 x 2000).  A chain layer reads its input as T-planes (planes of the transposed
-        # activation), written by the previous chain layer's epilogue or converted from fp32 at the chain's head, and writes
-        # T-planes for the next chain layer, N-planes for the next layer's weight gradient, fp32 only where an fp32 kernel follows.
-        self.chain = set()
-        if self.split_wgrad_wide:
-            # (bf16x3: 1024 -- with the 400-wide layers in the chain one p = 1 gradient check of G13 measures 1.1e-5; f16x2: 384 -- all of
-            #  config 3's checks hold 1e-5 and the step gains 13 %: 198 -> 225 steps/s)
-            cmin = 384 if self.split_f16_wide else 1024
-            self.chain = {l for l in range(1, L - 1) if self.wide_kinds[l] == 0 and in_w[l] >= cmin and widths[l] >= cmin}
-        if self.chain:                      # (only under split_wgrad_wide: f16w is set)
-            self.wT = {l: ops.mlp_planes_alloc(in_w[l], widths[l], False, dev, f16=f16w) for l in self.chain}      # planes of W^T
-            self.wN = {l: ops.mlp_planes_alloc(widths[l], in_w[l], False, dev, f16=f16w) for l in self.chain}      # planes of W
-            self.xT = {l: ops.mlp_planes_alloc(in_w[l], R, False, dev, f16=f16w) for l in self.chain}              # T-planes of the layer input
-            self.dzT = {l: ops.mlp_planes_alloc(widths[l], R, False, dev, f16=f16w) for l in self.chain}           # T-planes of dZ_l
-            if not f16w:
-                self._init_wide_ones()
-            self._wide_packed = False
+        # what the forward writes as fp32 (None: planes only), the plane copies, and -- whole-stack path -- the same for every dZ_l
+        self.acts_out = [None if only else a for a, only in zip(self.acts, self.encoder_plan.acts_planes_only)]
+        self.act_planes, self.dz_planes = [None] * L, [None] * L
+        self.dz = self.dz_out = self.signmasks = self.group_ws = None
+        if self.fused_backward:
+            self._allocate_whole_stack(R)
+        else:
+            self._allocate_per_layer(R)
         if self.head is not None:
             self.head_part = torch.empty(((R + 255) // 256, n if isinstance(self.head, ls.SoftclipLayer) else 1), **f32)
             self._head_src = hp = self.head.r if isinstance(self.head, ls.RescaleLayer) else self.head.max_abs_bound
@@ -391,20 +394,67 @@ class _FusedTrainer:
             self.head_learnable = isinstance(hp, nn.Parameter)
             self.dpre = torch.empty((R, n), **f32)
 
-    def _init_wide_ones(self):
-        """The fused epilogues of the wide chain never touch the constant-1 column of the N-planes they fill: written once here."""
-        if not self.chain:
-            return
-        L, R = len(self.linears), self._enc_rows()
+    def _allocate_whole_stack(self, R):
+        """Buffers of the one-launch backward chain and the grouped weight gradients."""
+        dev, ep = self.device, self.encoder_plan
         widths = [lin.out_features for lin in self.linears]
-        for l in self.chain:
-            if l + 1 < L and self.wide_kinds[l + 1] == 0:
-                ops.mlp_planes_from_f32(torch.zeros((R, widths[l]), dtype=torch.float32, device=self.device), True, out=self.xin_planes[l + 1],
+        shapes = [tuple(lin.weight.shape) for lin in self.linears]
+        self.dz = [torch.empty((R, w), dtype=torch.float32, device=dev) for w in widths[:-1]]       # dZ_l for the weight gradients
+        self.dz_out = [None if only else d for d, only in zip(self.dz, ep.dz_planes_only)]
+        # sign bits of every hidden activation, written by the fused forward, read by the fused backward chain
+        self.signmasks = ops.mlp_signmask_alloc(R, len(widths) - 1, dev) + [None]
+        if not ep.split_wgrad:
+            self.group_ws = ops.mlp_wgrad_workspace(R, shapes, dev)
+            return
+        for l, kind in enumerate(ep.kinds):
+            if kind == 0:                                # dW_l = dZ_l^T acts_{l-1} on the bf16 / fp16 matrix cores
+                self.act_planes[l - 1] = ops.mlp_planes_alloc(R, widths[l - 1], True, dev, f16=ep.split_f16)
+                self.dz_planes[l] = ops.mlp_planes_alloc(R, widths[l], False, dev, f16=ep.split_f16)
+        self.group_ws = ops.mlp_wgrad_split_workspace(R, shapes, dev)
+
+    def _allocate_per_layer(self, R):
+        """Buffers of the per-layer backward body: the rotating dZ buffers and the fp32 weight-gradient workspace; with split weight
+        gradients the plane copies of their operands; for the chain layers T-plane operands and plane copies of the weights."""
+        dev, ep = self.device, self.encoder_plan
+        L = len(self.linears)
+        widths, in_w = [lin.out_features for lin in self.linears], [lin.in_features for lin in self.linears]
+        self.dbuf = [torch.empty((R, max(widths + [self.n])), dtype=torch.float32, device=dev) for _ in range(3)]
+        nb = C.c_size_t(); need = 0
+        for lin in self.linears:
+            _lib.check(_lib.load().clica_linear_wgrad_workspace_bytes(R, lin.out_features, lin.in_features, C.byref(nb)), "wgrad ws")
+            need = max(need, nb.value)
+        self.wgrad_ws = torch.zeros(need, dtype=torch.uint8, device=dev)
+        if not ep.split_wgrad_wide:
+            return
+        # (f16x2: a tensor of the Split16 state = (family, layer): activations by the layer they feed, gradients and weights by their layer)
+        f16w, split = ep.split_f16_wide, [k == 0 for k in ep.wide_kinds]
+        self.xin_planes = [ops.mlp_planes_alloc(R, in_w[l], True, dev, f16=f16w) if split[l] else None for l in range(L)]
+        self.dzw_planes = [ops.mlp_planes_alloc(R, widths[l], False, dev, f16=f16w) if split[l] else None for l in range(L)]
+        self.wide_ws = max((ops.mlp_wgrad_split_workspace(R, [tuple(self.linears[l].weight.shape)], dev) for l in range(L) if split[l]),
+                           key=lambda t: t.numel(), default=None)
+        if not ep.chain:
+            return
+        # A chain layer reads its input as T-planes (planes of the transposed activation), written by the previous chain layer's epilogue
+        # or converted from fp32 at the chain's head, and writes T-planes for the next chain layer, N-planes for the next layer's weight
+        # gradient, fp32 only where an fp32 kernel follows.
+        self.wT = {l: ops.mlp_planes_alloc(in_w[l], widths[l], False, dev, f16=f16w) for l in ep.chain}      # planes of W^T
+        self.wN = {l: ops.mlp_planes_alloc(widths[l], in_w[l], False, dev, f16=f16w) for l in ep.chain}      # planes of W
+        self.xT = {l: ops.mlp_planes_alloc(in_w[l], R, False, dev, f16=f16w) for l in ep.chain}              # T-planes of the layer input
+        self.dzT = {l: ops.mlp_planes_alloc(widths[l], R, False, dev, f16=f16w) for l in ep.chain}           # T-planes of dZ_l
+        self._wide_packed = False
+        # the fused epilogues of the chain never touch the constant-1 column of the N-planes they fill: written once here
+        for l in ep.chain:
+            if split[l + 1]:
+                ops.mlp_planes_from_f32(torch.zeros((R, widths[l]), dtype=torch.float32, device=dev), True, out=self.xin_planes[l + 1],
                                         **self._s16w(0, l + 1))
 
     def _s16w(self, family: int, index: int) -> dict:
         """Keyword arguments that name a tensor of the f16x2 state for the per-layer producers (empty in the bf16x3 arithmetic)."""
         return dict(state=self.s16, tensor=(family, index)) if self.split_f16_wide else {}
+
+    def _s16l(self, l: int) -> dict:
+        """... that name a chain layer of the f16x2 state for the split GEMMs (linear_split_fwd / linear_split_dgrad)."""
+        return dict(state=self.s16, layer=l) if self.split_f16_wide else {}
 
     # -------------------------------------------------------------------------------- data
     def sample(self):
@@ -450,49 +500,12 @@ class _FusedTrainer:
         self._packed_current = True
 
     def forward(self):
-        cur = self.x
-        L = len(self.linears)
         self._planes_on_current_scales = True      # (saved_activation: the plane copies this pass writes are scaled by the scales in force NOW)
         if self.fused_forward:
-            # one launch for the whole stack, activation panel resident in LDS (csrc/fused_mlp.hip)
-            ws = [lin.weight for lin in self.linears]
-            if not self._packed_current:
-                self.pack()
-            mix = None
-            if self._x_pending:          # latents in, x = g(z) computed in the kernel prologue and stored to self.x
-                cur, mix, self._x_pending = self.z[:self.x.shape[0]], (self.gW, self.g_slope, self.x), False
-            if self.split_bf16:
-                ops.mlp_fwd_split(cur, ws, [lin.bias for lin in self.linears], self.acts_out, self.packed, self.slope,
-                                  signmasks=self.signmasks, mix=mix, planes=self.act_planes if self.split_wgrad else None, state=self.s16)
-            else:
-                ops.mlp_fwd(cur, ws, [lin.bias for lin in self.linears], self.acts, self.slope, packed=self.packed,
-                            signmasks=self.signmasks, mix=mix)
-            cur = self.acts[-1]
+            self._forward_whole_stack()
         else:
-            wide, chain = self.split_wgrad_wide, self.chain
-            if chain and not (self._wide_packed and self._packed_current):
-                for l in chain:                             # plane copies of the CURRENT weights, both orientations
-                    ops.mlp_planes_from_f32_t(self.linears[l].weight, out=self.wT[l], **self._s16w(2, l))
-                    ops.mlp_planes_from_f32(self.linears[l].weight, False, out=self.wN[l], **self._s16w(2, l))
-                self._wide_packed = self._packed_current = True
-            R = self.x.shape[0]
-            for l, lin in enumerate(self.linears):
-                fed = (l - 1) in chain                      # the previous layer's epilogue already wrote this layer's plane operands
-                if wide and self.wide_kinds[l] == 0 and not fed:        # this layer's input as bf16 planes for its weight gradient
-                    ops.mlp_planes_from_f32(cur, True, out=self.xin_planes[l], **self._s16w(0, l))
-                if l in chain:
-                    if not fed:
-                        ops.mlp_planes_from_f32_t(cur, out=self.xT[l], **self._s16w(0, l))
-                    nxt = (l + 1) in chain
-                    out = None if nxt else self.acts[l]
-                    ops.linear_split_fwd(self.xT[l], self.wT[l], lin.bias, R, lin.out_features, lin.in_features, l < L - 1, self.slope,
-                                         yT=self.xT[l + 1] if nxt else None,
-                                         yN=self.xin_planes[l + 1] if (l + 1 < L and self.wide_kinds[l + 1] == 0) else None, yN_ones=True, y=out,
-                                         **(dict(state=self.s16, layer=l) if self.split_f16_wide else {}))
-                    cur = out
-                    continue
-                ops.linear_fwd(cur, lin.weight, lin.bias, leaky=(l < L - 1), slope=self.slope, out=self.acts[l])
-                cur = self.acts[l]
+            self._forward_per_layer()
+        cur = self.acts[-1]
         if self.head is not None:
             lib, st = _lib.load(), _lib.stream_ptr()
             R, n = cur.shape
@@ -502,6 +515,48 @@ class _FusedTrainer:
             else:
                 _lib.check(lib.clica_softclip_fwd(cur.data_ptr(), n, self.head_param.data_ptr(), self.y.data_ptr(), n, R, n, st),
                            "clica_softclip_fwd")
+
+    def _forward_whole_stack(self):
+        """One launch for the whole stack, activation panel resident in LDS (csrc/fused_mlp.hip)."""
+        cur, mix = self.x, None
+        ws = [lin.weight for lin in self.linears]
+        if not self._packed_current:
+            self.pack()
+        if self._x_pending:          # latents in, x = g(z) computed in the kernel prologue and stored to self.x
+            cur, mix, self._x_pending = self.z[:self.x.shape[0]], (self.gW, self.g_slope, self.x), False
+        if self.split_bf16:
+            ops.mlp_fwd_split(cur, ws, [lin.bias for lin in self.linears], self.acts_out, self.packed, self.slope,
+                              signmasks=self.signmasks, mix=mix, planes=self.act_planes if self.split_wgrad else None, state=self.s16)
+        else:
+            ops.mlp_fwd(cur, ws, [lin.bias for lin in self.linears], self.acts, self.slope, packed=self.packed,
+                        signmasks=self.signmasks, mix=mix)
+
+    def _forward_per_layer(self):
+        """One GEMM per layer: fp32 MFMA, or -- chain layers -- the split GEMM on T-plane operands; the inputs of the split weight
+        gradients are converted to planes on the way."""
+        cur, chain = self.x, self.chain
+        L, R = len(self.linears), self.x.shape[0]
+        split = [k == 0 for k in self.wide_kinds] or [False] * L      # layers whose weight gradient reads plane copies
+        if chain and not (self._wide_packed and self._packed_current):
+            for l in chain:                             # plane copies of the CURRENT weights, both orientations
+                ops.mlp_planes_from_f32_t(self.linears[l].weight, out=self.wT[l], **self._s16w(2, l))
+                ops.mlp_planes_from_f32(self.linears[l].weight, False, out=self.wN[l], **self._s16w(2, l))
+            self._wide_packed = self._packed_current = True
+        for l, lin in enumerate(self.linears):
+            fed = (l - 1) in chain                      # the previous layer's epilogue already wrote this layer's plane operands
+            if split[l] and not fed:                    # this layer's input as planes for its weight gradient
+                ops.mlp_planes_from_f32(cur, True, out=self.xin_planes[l], **self._s16w(0, l))
+            if l in chain:
+                if not fed:
+                    ops.mlp_planes_from_f32_t(cur, out=self.xT[l], **self._s16w(0, l))
+                nxt = (l + 1) in chain
+                cur = None if nxt else self.acts[l]
+                ops.linear_split_fwd(self.xT[l], self.wT[l], lin.bias, R, lin.out_features, lin.in_features, l < L - 1, self.slope,
+                                     yT=self.xT[l + 1] if nxt else None, yN=self.xin_planes[l + 1] if split[l + 1] else None, yN_ones=True,
+                                     y=cur, **self._s16l(l))
+            else:
+                ops.linear_fwd(cur, lin.weight, lin.bias, leaky=(l < L - 1), slope=self.slope, out=self.acts[l])
+                cur = self.acts[l]
 
     def _head_backward(self):
         """d loss / d (pre-head output): the head's backward (and its parameter gradient), or dy itself."""
@@ -612,122 +667,96 @@ class _FusedTrainer:
 
     def backward(self):
         g = self._head_backward()
-        L = len(self.linears)
-        main = torch.cuda.current_stream(self.device) if self.device.type == "cuda" else None
-        side = self.side_stream
-        two = side is not None and main is not None
         if self.fused_backward:
-            # (1) the data-gradient chain in one launch; (2) the weight-gradient GEMMs
-            st = self.stamps
+            self._backward_whole_stack(g)
+        else:
+            self._backward_per_layer(g)
+
+    def _backward_whole_stack(self, g):
+        """(1) the data-gradient chain in one launch; (2) the grouped weight gradients -- under data parallelism with the layers'
+        slices of the gradient arena handed to the buckets, in two halves where that is planned."""
+        L, st, buckets = len(self.linears), self.stamps, self.buckets
+        if st:
+            ops.stamp(st["mlp_dgrad"], 0)
+        self.backward_chain(g)
+        if self._guard_rides:                      # this rank's verdict into the slot the first gradient bucket carries
+            self.s16.poison_export(self._guard_slot)
+        if st:
+            ops.stamp(st["mlp_dgrad"], 1)
+        if buckets is None:
             if st:
-                ops.stamp(st["mlp_dgrad"], 0)
-            self.backward_chain(g)
-            if self._guard_rides:                      # this rank's verdict into the slot the first gradient bucket carries
-                self.s16.poison_export(self._guard_slot)
+                ops.stamp(st["mlp_wgrad"], 0)
+            self.weight_grads(g)
             if st:
-                ops.stamp(st["mlp_dgrad"], 1)
-                if self.grouped_wgrad and self.buckets is None:
-                    ops.stamp(st["mlp_wgrad"], 0)
-                    self.weight_grads(g)
-                    ops.stamp(st["mlp_wgrad"], 1)
-                    return
-            if self.grouped_wgrad:
-                if self.buckets is not None and self.wgrad_halves:
-                    h = self._half
-                    self.weight_grads(g, layers=range(h, L))          # the head parameter's slot rides in the first slice
-                    for i in range(0, L - h):
-                        self.buckets.layer_done(i)                    # completion index i = layer L - 1 - i: all-reduce starts now ...
-                    self.weight_grads(g, layers=range(0, h))          # ... and runs under this launch
-                    for i in range(L - h, L):
-                        self.buckets.layer_done(i)
-                    self.buckets.wait()
-                    return
-                self.weight_grads(g)
-                if self.buckets is not None:
-                    for i in range(L):
-                        self.buckets.layer_done(i)
-                    self.buckets.wait()
-                return
-            use_two = two and self.buckets is None
-            if use_two:
-                side.wait_stream(main)
-            for i, l in enumerate(reversed(range(L))):
-                lin = self.linears[l]
-                gl = g if l == L - 1 else self.dz[l]
-                inp = self.acts[l - 1] if l > 0 else self.x
-                on_side = use_two and (i & 1)
-                with torch.cuda.stream(side) if on_side else _nullctx():
-                    ops.linear_wgrad(gl, inp, dW=self._gviews[id(lin.weight)], db=self._gviews[id(lin.bias)], accumulate=False,
-                                     ws=self.wgrad_ws2 if on_side else self.wgrad_ws)
-                if self.buckets is not None:
-                    self.buckets.layer_done(L - 1 - l)
-            if use_two:
-                main.wait_stream(side)
-            if self.buckets is not None:
-                self.buckets.wait()
+                ops.stamp(st["mlp_wgrad"], 1)
             return
-        # Per-layer path (wide encoders).  Two streams: wgrad_l (weight/bias gradients into the arena, + bucket
-        # all-reduce) runs on the side
-        # stream while the main stream continues the dZ chain with dgrad_l -- the two GEMMs are
-        # independent given dZ_l, and each hides the other's prologue / epilogue-store bubbles.  Three dZ
-        # buffers rotate; a buffer is rewritten only after the wgrad that read it has finished.
+        if self.wgrad_halves:
+            h = self._half
+            self.weight_grads(g, layers=range(h, L))          # the head parameter's slot rides in the first slice
+            for i in range(0, L - h):
+                buckets.layer_done(i)                         # completion index i = layer L - 1 - i: all-reduce starts now ...
+            self.weight_grads(g, layers=range(0, h))          # ... and runs under this launch
+            for i in range(L - h, L):
+                buckets.layer_done(i)
+        else:
+            self.weight_grads(g)
+            for i in range(L):
+                buckets.layer_done(i)
+        buckets.wait()
+
+    def _backward_per_layer(self, g):
+        """Two streams: wgrad_l (weight / bias gradients into the arena, + bucket all-reduce) runs on the side stream while the main
+        stream continues the dZ chain with dgrad_l -- the two GEMMs are independent given dZ_l, and each hides the other's prologue /
+        epilogue-store bubbles.  Three dZ buffers rotate; a buffer is rewritten only after the wgrad that read it has finished."""
+        L, R, chain, side = len(self.linears), self.x.shape[0], self.chain, self.side_stream
+        main = torch.cuda.current_stream(self.device) if self.device.type == "cuda" else None
+        two = side is not None and main is not None
         reader_done = {}        # dZ buffer index -> event of the wgrad that reads it
         buf_of_g = None         # index into self.dbuf holding the current dZ (None: self.dy / self.dpre, or planes only)
         nxt = 0
-        chain = self.chain
-        R = self.x.shape[0]
         dzN_ready = dzT_ready = False       # dZ_l already sits in dzw_planes[l] / dzT[l] (written by a split data-gradient epilogue)
+
+        def take():             # the next dZ buffer, cut to dZ_{l-1}, once the wgrad that read it last is done (WAR)
+            if two and nxt in reader_done:
+                main.wait_event(reader_done.pop(nxt))
+            return self.dbuf[nxt][:, :lin.in_features]
         for l in reversed(range(L)):
             lin = self.linears[l]
             inp = self.acts[l - 1] if l > 0 else self.x
             if two:
                 side.wait_stream(main)                      # dZ_l is complete on main
-                with torch.cuda.stream(side):
-                    self._wgrad_layer(l, g, inp, self.wgrad_ws, planes_ready=dzN_ready)
-                    if self.buckets is not None:
-                        self.buckets.layer_done(L - 1 - l)
-                    if buf_of_g is not None:
-                        ev = torch.cuda.Event(); ev.record(side); reader_done[buf_of_g] = ev
-            else:
+            with torch.cuda.stream(side) if two else _nullctx():
                 self._wgrad_layer(l, g, inp, self.wgrad_ws, planes_ready=dzN_ready)
                 if self.buckets is not None:
                     self.buckets.layer_done(L - 1 - l)
-            if l > 0 and l in chain:
+                if two and buf_of_g is not None:
+                    ev = torch.cuda.Event(); ev.record(side); reader_done[buf_of_g] = ev
+            if l == 0:
+                break
+            if l in chain:
                 # dZ_{l-1} = (dZ_l W_l) * LeakyReLU'(acts_{l-1}) on the split bodies: T-planes in, gate from the T-planes of the
                 # layer input, T-planes out for the next chain layer, N-planes out for the weight gradient of layer l - 1
                 if not dzT_ready:
                     ops.mlp_planes_from_f32_t(g, out=self.dzT[l], **self._s16w(1, l))
-                prev = (l - 1) in chain
-                out = None
-                if not prev:
-                    if two and nxt in reader_done:
-                        main.wait_event(reader_done.pop(nxt))
-                    out = self.dbuf[nxt][:, :lin.in_features]
+                prev = (l - 1) in chain                     # dZ_{l-1} goes on as T-planes: no fp32 copy
+                out = None if prev else take()
                 dxN = self.dzw_planes[l - 1] if self.wide_kinds[l - 1] == 0 else None
                 ops.linear_split_dgrad(self.dzT[l], self.wN[l], self.xT[l], self.slope, R, lin.out_features, lin.in_features,
-                                       dxT=self.dzT[l - 1] if prev else None, dxN=dxN, dx=out,
-                                       **(dict(state=self.s16, layer=l) if self.split_f16_wide else {}))
+                                       dxT=self.dzT[l - 1] if prev else None, dxN=dxN, dx=out, **self._s16l(l))
                 dzT_ready, dzN_ready = prev, dxN is not None
-                g = out
-                if out is not None:
-                    buf_of_g = nxt
-                    nxt = (nxt + 1) % len(self.dbuf)
-                else:
-                    buf_of_g = None
-            elif l > 0:
-                if two and nxt in reader_done:
-                    main.wait_event(reader_done.pop(nxt))    # WAR: the wgrad that read this buffer is done
-                out = self.dbuf[nxt][:, :lin.in_features]
+            else:
+                out = take()
                 ops.linear_dgrad(g, lin.weight, inp, self.slope, out=out)
-                g, buf_of_g = out, nxt
-                nxt = (nxt + 1) % len(self.dbuf)
                 dzN_ready = dzT_ready = False
+            g, buf_of_g = out, (nxt if out is not None else None)
+            if out is not None:
+                nxt = (nxt + 1) % len(self.dbuf)
         if two:
             main.wait_stream(side)
         if self.buckets is not None:
             self.buckets.wait()
-        if self.dp and self.s16 is not None and not self._guard_rides:
-            # per-layer path: producers run until the last layer's gradient, so the verdict is reduced on its own (4 bytes) behind them
+        if self.dp and self.s16 is not None:
+            # producers run until the last layer's gradient, so the verdict is reduced on its own (4 bytes) behind them
             self.s16.poison_export(self._guard_slot)
             dist.all_reduce(self._guard_slot, op=dist.ReduceOp.SUM, group=self.pg)
 
@@ -758,7 +787,7 @@ class _FusedTrainer:
         if self.s16 is not None and not self._s16_calibrated:
             self.calibrate_scales(sample)
         self._packed_current = False          # a step always re-packs (parameters may have been set from outside)
-        fused = (self.fused_forward or self.fused_backward) and self.device.type == "cuda"
+        fused = self.fused_forward and self.device.type == "cuda"
         if not (sample and fused and self._pack_sample_merged()):
             if sample:
                 self.sample()
@@ -857,11 +886,8 @@ class _FusedTrainer:
 
     def _arith_name(self) -> str:
         """The `arith` string of arith_state() (no device read)."""
-        if self.s16 is not None:
-            return "f16x2" if self.split_f16 else "f16x2 (per-layer wide path; narrow layers native fp32 MFMA)"
-        if not (self.split_bf16 or self.split_wgrad_wide):
-            return "native_fp32"
-        return "bf16x3"
+        ep = self.encoder_plan
+        return ep.arith + (" (per-layer wide path; narrow layers native fp32 MFMA)" if ep.split_f16_wide else "")
 
     # -------------------------------------------------------------------------------- checkpoints
     STATE_FORMAT, STATE_VERSION = "cl_ica_amd.trainer", 1
@@ -1283,7 +1309,7 @@ class ContrastiveTrainer(_FusedTrainer):
                     wgrad_halves=bool(self.wgrad_halves), wgrad_group_workspace_bytes=int(self.group_ws.numel()) if self.group_ws is not None else 0,
                     gradient_buckets=[list(b) for b in (self.buckets.buckets if self.buckets is not None else [])],
                     gradient_arena_elements=int(self.grad_arena.numel()), grad_scale=1.0 / ranks, collectives_per_step=coll,
-                    encoder_path="whole-stack" if self.fused_forward else "per-layer", split_bf16=bool(self.split_bf16),
+                    encoder_path=self.encoder_plan.path, split_bf16=self.split_bf16,
                     graph_captured=self.graph is not None)
 
 
@@ -1350,5 +1376,5 @@ class SupervisedTrainer(_FusedTrainer):
 
     def plan_summary(self) -> dict:
         return dict(world=1, batch_per_rank=self.B, encoder_rows=self._enc_rows(), objective="mse",
-                    encoder_path="whole-stack" if self.fused_forward else "per-layer", split_bf16=bool(self.split_bf16),
+                    encoder_path=self.encoder_plan.path, split_bf16=self.split_bf16,
                     graph_captured=self.graph is not None)

@@ -5,7 +5,8 @@ plan_summary().  Two commits whose outputs are byte-identical run the same launc
 at both).  The call names are what _lib.check reports under CLICA_DEBUG_SYNC=1; clica_mlp_chain_tail_supported -- a host-side question to
 the library's planner that launches nothing -- is left out of the list, so that WHEN a trainer asks it does not count.
     python tools/engine_digest.py OUT.jsonl          # the digest
-    python tools/engine_digest.py --eager            # prints steps/s of 300 eager steps at B = 6144 behind 50 warm-up steps (one event pair)"""
+    python tools/engine_digest.py --eager            # prints steps/s of 300 eager steps at B = 6144 behind 50 warm-up steps (one event pair)
+    python tools/engine_digest.py --eager --hidden 100,640,640,100      # ... with these hidden widths (here: the per-layer path)"""
 import hashlib, json, os, sys
 os.environ["CLICA_DEBUG_SYNC"] = "1" if "--eager" not in sys.argv else "0"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -108,11 +109,22 @@ def configs():
     yield "per-layer/f16x2", dict(p=2, hidden=(100, 640, 640, 100))
     yield "per-layer/bf16x3", dict(p=2, hidden=(100, 640, 640, 100), arith="bf16")
     yield "dry_ranks=2", dict(p=2, process_group=dist.group.WORLD, force_collectives=True, dry_ranks=2)
+    # the encoder paths the rows above do not reach (EncoderPlan): split forward and chain with fp32 grouped weight gradients; the plain
+    # per-layer path; split weight gradients with an empty chain; a narrow encoder kept off the whole-stack kernels; the per-layer body
+    # without the side stream.  (A single-Linear encoder -- fused_forward without fused_backward -- is not here: get_mlp refuses it.)
+    yield "two-layer/f16x2", dict(hidden=(100,))
+    yield "per-layer/native_fp32", dict(hidden=(100, 640, 640, 100), split=False)
+    yield "per-layer/no-chain", dict(hidden=(100, 600, 100))
+    yield "per-layer/forced", dict(hidden=(100, 500, 500, 100), fused_forward=False)
+    yield "per-layer/f16x2/one-stream", dict(hidden=(100, 640, 640, 100), overlap_backward=False)
 
 
 def eager_rate():
+    hidden = [100, 500, 500, 500, 500, 100]
+    if "--hidden" in sys.argv:           # e.g. --hidden 100,640,640,100: the same loop on the per-layer path
+        hidden = [int(w) for w in sys.argv[sys.argv.index("--hidden") + 1].split(",")]
     torch.manual_seed(0)
-    f = encoders.get_mlp(N, N, [100, 500, 500, 500, 500, 100])
+    f = encoders.get_mlp(N, N, hidden)
     tr = ContrastiveTrainer(f, torch.randn(3, N, N) / N ** 0.5, SamplerSpec(n=N, seed=5), batch_size=6144, p=2, lr=1e-4, device="cuda")
     for _ in range(50):
         tr.step()

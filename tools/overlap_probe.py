@@ -44,7 +44,8 @@ def mask_rows(m, r0, r1):
 def chain_rows(g, r0, r1):
     ops.mlp_dgrad_chain_split(g[r0:r1], ws, tr.packed_t, [rows(tr.dz_out[l - 1], r0, r1) for l in chain], tr.slope,
                               masks_chain=[mask_rows(tr.signmasks[l - 1], r0, r1) for l in chain],
-                              planes=[plane_rows(tr.dz_planes[l - 1], r0, r1) for l in chain])
+                              planes=[plane_rows(tr.dz_planes[l - 1], r0, r1) for l in chain],
+                              state=tr.s16)       # (f16x2 trainer: its planes and pack are 4 B/element -- the bf16x3 kernel would overrun them)
 
 
 def loss_two_calls(between):
