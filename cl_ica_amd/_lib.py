@@ -225,6 +225,13 @@ SIGNATURES: Dict[str, list] = {
     "clica_bn2d_nhwc_act_fwd_eval": [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_i32, C.c_float, C.c_float, c_f32p, C.c_void_p],
     "clica_bn2d_nhwc_act_bwd": [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_i32, C.c_float, c_f32p, c_f32p, c_f32p, c_f32p,
                                 C.c_void_p, c_size, C.c_void_p],
+    "clica_bn2d_nhwc_maxpool_workspace_bytes": [c_i64, c_i32, c_i32, c_i32, C.POINTER(c_size)],
+    "clica_bn2d_nhwc_act_maxpool_fwd_train": [c_f32p, c_f32p, c_f32p, c_i64, c_i32, c_i32, c_i32, C.c_float, C.c_float, C.c_float, c_f32p,
+                                              c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, c_size, C.c_void_p],
+    "clica_bn2d_nhwc_act_maxpool_fwd_eval": [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_i32, c_i32, c_i32, C.c_float, C.c_float, c_f32p,
+                                             C.c_void_p],
+    "clica_bn2d_nhwc_act_maxpool_bwd": [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_i32, c_i32, c_i32, C.c_float, c_f32p,
+                                        c_f32p, c_f32p, C.c_void_p, c_size, C.c_void_p],
     "clica_avgpool2d_global_nhwc_fwd": [c_f32p, c_i64, c_i32, c_i32, c_f32p, C.c_void_p],
     "clica_avgpool2d_global_nhwc_bwd": [c_f32p, c_i64, c_i32, c_i32, c_f32p, C.c_void_p],
     "clica_conv_im2col_k4s2": [c_f32p, c_i64, c_i32, c_i32, c_i32, c_f32p, C.c_void_p],

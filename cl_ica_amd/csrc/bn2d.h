@@ -128,6 +128,84 @@ static inline size_t rows_workspace_bytes(int64_t M, int32_t C) {
   return align_up((size_t)3 * (size_t)rows_geometry(M, C).S * (size_t)C * sizeof(float), 16);
 }
 
+// ------------------------------------------------------------------------------------------------ channels-last stem unit with the max-pool
+// P = maxpool 3x3 / stride 2 / pad 1 of lrelu(gamma xhat + beta), floor mode, on x[N, H, W, C] (bn2d_nhwc.hip).  The lanes are those of
+// the "rows" geometry (`vec` channels per lane, `lpr` lanes along C, rps = 256 / lpr pixel slots per workgroup, grid.x = chunks), the
+// statistics launch and the merge of its S partials are the unit's own (rows_geometry(N H W, C)).
+//   forward: a slot owns an output pixel (n, ho, wo) and reads its <= 9 inputs itself; the N Ho Wo output pixels are cut into `Tf`
+//     runs of `tile_f` (as the apply launches above).  No LDS beyond the merge.
+//   backward sums: a slot owns a window as in the forward -- a window's gradient lands on one pixel, its first maximum, so the sums over
+//     pixels are sums over windows --; the N Ho Wo windows are cut into `Sb` runs of `per_b`, one workgroup and one partial per run and
+//     channel, Sb sized and capped as S is.  No LDS beyond the wave merge.
+//   backward apply: one TILE = (image, band of BH output rows, band of BW output columns) for a chunk of lpr vec channels.  A workgroup
+//     first leaves, for each of the tile's (BH + 1) x (BW + 1) windows -- its own and the row below / column right of them, which share pixels
+//     with it --, dP gate(y) (a float) and the position of the window's first maximum (a byte) per channel in LDS, then a slot owns an
+//     input pixel of rows 2 ho0 .. 2 (ho0 + BH) - 1, columns 2 wo0 .. 2 (wo0 + BW) - 1 and gathers its <= 4 windows.  LDS per workgroup:
+//     (BH + 1)(BW + 1) lpr vec <= kPoolRowsLdsFloats entries of 5 bytes (30 KB), whatever the plane: BW <= 8 columns, then as many rows
+//     as fit, both evened out over the plane (C = 64: 8 x 8 windows = 16 x 16 pixels per tile; a chunk of 256 channels: 3 x 4).
+//     The N nbh nbw tiles in (image, row band, column band) order are cut into `Ta` runs of `per_a` tiles, each workgroup merging the Sb
+//     partials (`msb` per merging thread) as the unit's backward apply does.
+// Everything is a function of (N, H, W, C) alone; the only limit on a plane is H, W <= kPoolRowsMaxSide (int arithmetic inside a tile).
+constexpr int kPoolRowsLdsFloats = 6144;
+constexpr int kPoolRowsMaxSide = 1 << 15;
+constexpr int kPoolRowsMaxBand = 8;
+
+struct PoolRows {
+  Rows rows;                      // lanes; the statistics launch and the merge of its partials
+  int Ho, Wo, BH, BW, nbh, nbw;   // output plane; output rows / columns per tile; bands per plane
+  int Sb, msb;                    // backward sums: runs of windows = partials per channel; per merging thread
+  int64_t per_b;
+  int64_t tiles;                  // backward apply: N nbh nbw tiles
+  int Ta;                         //   in runs of per_a
+  int64_t per_a;
+  int Tf;                         // forward: runs of output pixels
+  int64_t tile_f;                 // a multiple of rps
+};
+
+static inline bool pool_rows_fits(int32_t H, int32_t W, int32_t C) {
+  return H >= 1 && W >= 1 && H <= kPoolRowsMaxSide && W <= kPoolRowsMaxSide && C >= 1 && C <= kMaxC;
+}
+
+static inline PoolRows pool_rows_geometry(int64_t N, int32_t C, int32_t H, int32_t W) {
+  PoolRows g;
+  g.rows = rows_geometry(N * (int64_t)H * W, C);
+  const Rows& r = g.rows;
+  g.Ho = pool_out(H); g.Wo = pool_out(W);
+  static_assert(kPoolRowsLdsFloats / kThreads >= 2 * (kPoolRowsMaxBand + 1), "a tile holds at least one row of windows and the row below");
+  const int nwin = kPoolRowsLdsFloats / (r.lpr * r.vec);      // (lpr vec <= 256: >= 24 windows)
+  g.nbw = (int)ceil_div((int64_t)g.Wo, (int64_t)kPoolRowsMaxBand);
+  g.BW = (int)ceil_div((int64_t)g.Wo, (int64_t)g.nbw);
+  int bh = nwin / (g.BW + 1) - 1;
+  if (bh > g.Ho) bh = g.Ho;
+  g.nbh = (int)ceil_div((int64_t)g.Ho, (int64_t)bh);
+  g.BH = (int)ceil_div((int64_t)g.Ho, (int64_t)g.nbh);        // <= bh: (BH + 1)(BW + 1) <= nwin
+  g.tiles = N * g.nbh * g.nbw;
+  const int64_t Mo = N * g.Ho * g.Wo;
+  int64_t cap = (int64_t)kRowsMergeLoads * r.mg;
+  if (cap > kRowsMaxSplits) cap = kRowsMaxSplits;
+  int64_t s = ceil_div(Mo, (int64_t)kRowsSplitSteps * r.rps);
+  if (s > cap) s = cap;
+  g.per_b = ceil_div(Mo, s);
+  g.Sb = (int)ceil_div(Mo, g.per_b);
+  g.msb = (int)ceil_div((int64_t)g.Sb, (int64_t)r.mg);
+  int64_t fill = kRowsMaxTiles / r.chunks;                    // workgroups along y that fill the part
+  if (fill < 1) fill = 1;
+  g.per_a = ceil_div(g.tiles, fill < g.tiles ? fill : g.tiles);
+  g.Ta = (int)ceil_div(g.tiles, g.per_a);
+  int64_t f = ceil_div(Mo, fill);
+  if (f < (int64_t)kRowsTileSteps * r.rps) f = (int64_t)kRowsTileSteps * r.rps;
+  g.tile_f = ceil_div(f, (int64_t)r.rps) * r.rps;
+  g.Tf = (int)ceil_div(Mo, g.tile_f);
+  return g;
+}
+
+// forward: the unit's three planes [S][C]; backward: two planes [Sb][C] in the same buffer
+static inline size_t pool_rows_workspace_bytes(int64_t N, int32_t C, int32_t H, int32_t W) {
+  const PoolRows g = pool_rows_geometry(N, C, H, W);
+  const size_t s = (size_t)(g.rows.S > g.Sb ? g.rows.S : g.Sb);
+  return align_up((size_t)3 * s * (size_t)C * sizeof(float), 16);
+}
+
 // the statistics launch of clica_bn2d_act_fwd_train (bn2d.hip): partials [3][S][C] of geometry(N, HW) into `part`
 void launch_stats(hipStream_t st, const float* X, int64_t N, int32_t C, int32_t HW, float* part);
 

@@ -14,6 +14,10 @@
 // The reduction tree of a channel: per lane over its rows m0 + row, m0 + row + rps, ... (blocks of four rows two-pass in registers, as
 // bn2d.hip), the lanes of a wave that hold the channel by shuffles (lane l takes lane l + off, off = 32 .. lpr), the waves through LDS
 // in wave order, the splits as above.  It depends on (M, C) alone; AL only picks 16-byte accesses.
+// The stem unit with its max-pool, P = maxpool 3 x 3 / 2 / 1 of y, on the same lanes (bn2d.h, PoolRows): rows_stats_k, then
+// pool_rows_fwd_k, which merges and finishes as rows_apply_k and writes each output pixel's first maximum; inference: one launch;
+// backward: pool_rows_sums_k (a slot per window: the sums need no pixels) and pool_rows_bwd_apply_k, which recomputes y per tile of
+// windows and gathers dz per pixel.
 // No floating-point atomics, no arrival counters, nothing that waits inside a kernel: phases are ordered by the stream.
 #include "bn2d.h"
 
@@ -332,6 +336,303 @@ __global__ __launch_bounds__(kThreads) void avgpool_bwd_k(const float* __restric
   dx[t] = dy[(nk / HW) * C + (t - nk * C)] * inv;
 }
 
+// ------------------------------------------------------------------------------------------------ the stem unit with its max-pool
+// P = maxpool 3 x 3 / stride 2 / padding 1 of y = lrelu(gamma xhat + beta, slope), on x[N, H, W, C]; geometry: bn2d.h, PoolRows.
+//
+// The window (ho, wo) of the image at xn (= x + n H W C + c0), per channel of the lane: y of its pixels inside the plane in scan order
+// (rows, then columns), its maximum and the position 0 .. 8 of the maximum's first occurrence -- strict >, torch's rule and window_max's
+// of pool2d.hip, so the bits of that first maximum, signed zeros included -- and xhat of that pixel in xm.  The nine loads are issued
+// before the first comparison; a position outside the plane loads the window's centre, which is always inside, and never wins.
+template <int VEC, bool AL>
+__device__ __forceinline__ void window_first_max(const float* __restrict__ xn, int ho, int wo, int H, int W, int C, const bn::Norm* nm,
+                                                 const float* g, const float* b, float slope, float* m, int* code, float* xm) {
+  float v[9][VEC];
+  bool ok[9];
+#pragma unroll
+  for (int dy = 0; dy < 3; ++dy) {
+    const int hh = 2 * ho - 1 + dy;
+    const bool vr = hh >= 0 && hh < H;
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx) {
+      const int ww = 2 * wo - 1 + dx;
+      const bool vc = ww >= 0 && ww < W;
+      ok[dy * 3 + dx] = vr && vc;
+      load<VEC, AL>(xn + ((int64_t)(vr ? hh : 2 * ho) * W + (vc ? ww : 2 * wo)) * C, v[dy * 3 + dx]);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) { m[k] = -INFINITY; code[k] = 4; xm[k] = 0.f; }
+#pragma unroll
+  for (int p = 0; p < 9; ++p) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      const float xh = bn::xhat(v[p][k], nm[k]);
+      const float y = bn::fwd_xhat(xh, g[k], b[k], slope);      // (= bn::fwd: the unit's y)
+      if (ok[p] && y > m[k]) { m[k] = y; code[k] = p; xm[k] = xh; }
+    }
+  }
+}
+
+// forward: grid (chunks, Tf); a slot (Lane::row) owns an output pixel o = (n, ho, wo) of its run of `tile`.  TRAIN as rows_apply_k.
+template <int VEC, bool AL, bool TRAIN>
+__global__ __launch_bounds__(kThreads) void pool_rows_fwd_k(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                           const float* __restrict__ beta, int64_t Mo, int C, int H, int W, int Ho, int Wo,
+                                                           int lpr, int mg, int ms, int S, int64_t tile, float Mf, float eps, float momentum,
+                                                           float slope, const float* __restrict__ part, float* __restrict__ P,
+                                                           float* __restrict__ save_mean, float* __restrict__ save_invstd,
+                                                           float* running_mean, float* running_var) {
+  __shared__ float sh[TRAIN ? kMergeLds : 1];
+  __shared__ float shn[TRAIN ? 2 * kThreads : 1];          // mean, invstd of the chunk's channels
+  const Lane<VEC> ln(C, lpr);
+  bn::Norm nm[VEC];
+  if (TRAIN) {
+    const Merger mr(C, lpr, VEC);
+    const Stat t = merged_stat(mr, part, S, C, mg, ms, sh);
+    if (mr.first()) {
+      const bn::Norm n = bn::finish_train(t, x[mr.c], Mf, eps, momentum, mr.c, blockIdx.y == 0, save_mean, save_invstd, running_mean,
+                                          running_var);
+      shn[mr.ci] = n.mean; shn[kThreads + mr.ci] = n.invstd;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) nm[k] = bn::Norm{shn[ln.ci0 + k], shn[kThreads + ln.ci0 + k]};
+  }
+  if (!ln.in) return;
+  float g[VEC], b[VEC];
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) {
+    if (!TRAIN) nm[k] = bn::finish_eval(running_mean, running_var, ln.c0 + k, eps);
+    g[k] = gamma[ln.c0 + k]; b[k] = beta[ln.c0 + k];
+  }
+  const int HoWo = Ho * Wo;
+  const int64_t o0 = (int64_t)blockIdx.y * tile;
+  const int64_t o1 = o0 + tile < Mo ? o0 + tile : Mo;
+  for (int64_t o = o0 + ln.row; o < o1; o += ln.rps) {
+    const int64_t n = o / HoWo;
+    const int r = (int)(o - n * HoWo), ho = r / Wo, wo = r - ho * Wo;
+    float m[VEC], xm[VEC];
+    int code[VEC];
+    window_first_max<VEC, AL>(x + n * H * W * C + ln.c0, ho, wo, H, W, C, nm, g, b, slope, m, code, xm);
+    store<VEC, AL>(P + o * C + ln.c0, m);
+  }
+}
+
+// backward sums: grid (chunks, Sb) over runs of `per` output pixels, a slot per window as pool_rows_fwd_k.  A window's gated gradient
+// d = dP gate(y_max) lands on exactly one pixel, its first maximum, so over a channel
+//   sum over pixels of dz = sum over windows of d,      sum over pixels of dz xhat = sum over windows of d xhat(first maximum):
+// the sums need the windows, not the pixels -- no LDS staging, no halo.  The partial's tree: per lane over its windows in order, then
+// lanes and waves as rows_sums_k.
+template <int VEC, bool AL>
+__global__ __launch_bounds__(kThreads) void pool_rows_sums_k(const float* __restrict__ x, const float* __restrict__ dP,
+                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            const float* __restrict__ save_mean, const float* __restrict__ save_invstd,
+                                                            int64_t Mo, int C, int H, int W, int Ho, int Wo, int lpr, int64_t per,
+                                                            float slope, float* __restrict__ part) {
+  __shared__ float sh[VEC * bn::kColumnSumsLds];
+  const Lane<VEC> ln(C, lpr);
+  const int split = (int)blockIdx.y, S = (int)gridDim.y;
+  float s1[VEC], s2[VEC];
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) { s1[k] = 0.f; s2[k] = 0.f; }
+  if (ln.in) {
+    bn::Norm nm[VEC];
+    float g[VEC], b[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      nm[k] = bn::Norm{save_mean[ln.c0 + k], save_invstd[ln.c0 + k]};
+      g[k] = gamma[ln.c0 + k]; b[k] = beta[ln.c0 + k];
+    }
+    const int HoWo = Ho * Wo;
+    const int64_t o0 = (int64_t)split * per;
+    const int64_t o1 = o0 + per < Mo ? o0 + per : Mo;
+    for (int64_t o = o0 + ln.row; o < o1; o += ln.rps) {
+      const int64_t n = o / HoWo;
+      const int r = (int)(o - n * HoWo), ho = r / Wo, wo = r - ho * Wo;
+      float m[VEC], xm[VEC], d[VEC];
+      int code[VEC];
+      load<VEC, AL>(dP + o * C + ln.c0, d);
+      window_first_max<VEC, AL>(x + n * H * W * C + ln.c0, ho, wo, H, W, C, nm, g, b, slope, m, code, xm);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) bn::bwd_sums(s1[k], s2[k], bn::bwd_dz(d[k], m[k], slope), xm[k]);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) {
+    for (int off = 32; off >= lpr; off >>= 1) { s1[k] += __shfl_down(s1[k], off, 64); s2[k] += __shfl_down(s2[k], off, 64); }
+    bn::column_sums(s1[k], s2[k], sh + k * bn::kColumnSumsLds);
+  }
+  if ((int)threadIdx.x < lpr && ln.in) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      float* q = part + (size_t)split * C + ln.c0 + k;
+      q[0] = s1[k]; q[(size_t)S * C] = s2[k];
+    }
+  }
+}
+
+struct PoolPlane { int H, W, C, Ho, Wo, BH, BW, nbh, nbw; };
+
+// The positions of the first maxima of a lane's VEC channels, a byte each: one 4-byte LDS access when VEC = 4 (entries of 4 channels
+// start at multiples of 4).
+template <int VEC>
+__device__ __forceinline__ void codes_store(unsigned char* p, const int* code) {
+  if (VEC == 4) *reinterpret_cast<uint32_t*>(p) = (uint32_t)code[0] | (uint32_t)code[1] << 8 | (uint32_t)code[2] << 16 | (uint32_t)code[3] << 24;
+  else p[0] = (unsigned char)code[0];
+}
+template <int VEC>
+__device__ __forceinline__ void codes_load(const unsigned char* p, int* code) {
+  if (VEC == 4) {
+    const uint32_t u = *reinterpret_cast<const uint32_t*>(p);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) code[k] = (int)(u >> (8 * k) & 255u);
+  } else {
+    code[0] = p[0];
+  }
+}
+template <int VEC>
+__device__ __forceinline__ void lds_store(float* p, const float* v) {
+  if (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  else p[0] = v[0];
+}
+template <int VEC>
+__device__ __forceinline__ void lds_load(const float* p, float* v) {
+  if (VEC == 4) {
+    const float4 t = *reinterpret_cast<const float4*>(p);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else {
+    v[0] = p[0];
+  }
+}
+
+// dz of the tile's pixel (lh, lw) -- row 2 ho0 + lh, column 2 wo0 + lw of the plane -- for the lane's channels (entry ci0 of the chunk):
+// the gated gradients of the <= 4 windows that contain the pixel and whose first maximum it is, added in window order (ho, then wo), as
+// pool_dz of pool2d.hip.  hb / wb: the pixel is also row 0 of the window below / column 0 of the window to the right.
+template <int VEC>
+__device__ __forceinline__ void pool_rows_dz(const float* sd, const unsigned char* sc, int lh, int lw, bool hb, bool wb, int stride, int CH,
+                                             int ci0, float* dz) {
+  const int ha = lh >> 1, wa = lw >> 1, ph = (lh & 1) + 1, pw = (lw & 1) + 1;            // position (ph, pw) in window (ha, wa)
+  const int h2 = hb ? ha + 1 : ha, w2 = wb ? wa + 1 : wa;
+  const int o[4] = {(ha * stride + wa) * CH + ci0, (ha * stride + w2) * CH + ci0, (h2 * stride + wa) * CH + ci0,
+                    (h2 * stride + w2) * CH + ci0};
+  float d[4][VEC];
+  int c[4][VEC];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    lds_load<VEC>(sd + o[j], d[j]);
+    codes_load<VEC>(sc + o[j], c[j]);
+  }
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) {
+    float acc = c[0][k] == ph * 3 + pw ? d[0][k] : 0.f;
+    acc += wb && c[1][k] == ph * 3 ? d[1][k] : 0.f;
+    acc += hb && c[2][k] == pw ? d[2][k] : 0.f;
+    acc += hb && wb && c[3][k] == 0 ? d[3][k] : 0.f;
+    dz[k] = acc;
+  }
+}
+
+// backward apply: grid (chunks, Ta), a workgroup per run of `per` tiles; run 0 writes dgamma and dbeta.  Per tile every slot takes
+// windows i = row, row + rps, ... of the tile's staged (BH + 1) x (BW + 1) (the part inside the output plane) and leaves dP gate(y_max)
+// in sd and the position of the first maximum in sc, entry (window, channel of the chunk); after a barrier it takes pixels i = row,
+// row + rps, ... of the tile's own (row-major), gathers dz and writes dx.  Lanes without channels only keep the barriers company.
+template <int VEC, bool AL>
+__global__ __launch_bounds__(kThreads) void pool_rows_bwd_apply_k(const float* __restrict__ x, const float* __restrict__ dP,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                 const float* __restrict__ save_mean, const float* __restrict__ save_invstd,
+                                                                 PoolPlane g, int lpr, int mg, int ms, int S, int64_t tiles, int64_t per,
+                                                                 float Mf, float slope, const float* __restrict__ part,
+                                                                 float* __restrict__ dx, float* __restrict__ dgamma,
+                                                                 float* __restrict__ dbeta) {
+  __shared__ float sh[kMergeLds];
+  __shared__ float shs[2 * kThreads];                      // sum dz, sum dz xhat of the chunk's channels
+  __shared__ __attribute__((aligned(16))) float sd[kPoolRowsLdsFloats];
+  __shared__ __attribute__((aligned(16))) unsigned char sc[kPoolRowsLdsFloats];
+  const Lane<VEC> ln(g.C, lpr);
+  {
+    const Merger mr(g.C, lpr, VEC);
+    float a, b;
+    merged_sums(mr, part, S, g.C, mg, ms, sh, a, b);
+    if (mr.first()) {
+      if (blockIdx.y == 0) {
+        dgamma[mr.c] = b;
+        dbeta[mr.c] = a;
+      }
+      shs[mr.ci] = a; shs[kThreads + mr.ci] = b;
+    }
+    __syncthreads();
+  }
+  bn::Norm nm[VEC];
+  bn::Bwd bw[VEC];
+  float gm[VEC], bt[VEC];
+  if (ln.in) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      nm[k] = bn::Norm{save_mean[ln.c0 + k], save_invstd[ln.c0 + k]};
+      gm[k] = gamma[ln.c0 + k]; bt[k] = beta[ln.c0 + k];
+      bw[k] = bn::bwd_coeffs(gm[k], nm[k].invstd, shs[ln.ci0 + k], shs[kThreads + ln.ci0 + k], Mf);
+    }
+  }
+  const int CH = lpr * VEC, per_image = g.nbh * g.nbw, stride = g.BW + 1;
+  const int64_t t0 = (int64_t)blockIdx.y * per;
+  const int64_t t1 = t0 + per < tiles ? t0 + per : tiles;
+  for (int64_t t = t0; t < t1; ++t) {
+    const int64_t n = t / per_image;
+    const int r = (int)(t - n * per_image), bh = r / g.nbw, bwi = r - bh * g.nbw;
+    const int ho0 = bh * g.BH, wo0 = bwi * g.BW;
+    const int nh = g.BH < g.Ho - ho0 ? g.BH : g.Ho - ho0, nw = g.BW < g.Wo - wo0 ? g.BW : g.Wo - wo0;      // the tile's own windows
+    const int wh = nh + 1 < g.Ho - ho0 ? nh + 1 : g.Ho - ho0, ww = nw + 1 < g.Wo - wo0 ? nw + 1 : g.Wo - wo0;      // staged
+    const int ph = 2 * nh < g.H - 2 * ho0 ? 2 * nh : g.H - 2 * ho0, pw = 2 * nw < g.W - 2 * wo0 ? 2 * nw : g.W - 2 * wo0;      // own pixels
+    if (ln.in) {
+      const float* xn = x + n * g.H * g.W * g.C + ln.c0;
+      const float* dpn = dP + n * g.Ho * g.Wo * g.C + ln.c0;
+      for (int i = ln.row; i < wh * ww; i += ln.rps) {
+        const int lh = i / ww, lw = i - lh * ww, ho = ho0 + lh, wo = wo0 + lw;
+        float m[VEC], xm[VEC], d[VEC];
+        int code[VEC];
+        load<VEC, AL>(dpn + ((int64_t)ho * g.Wo + wo) * g.C, d);
+        window_first_max<VEC, AL>(xn, ho, wo, g.H, g.W, g.C, nm, gm, bt, slope, m, code, xm);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) d[k] = bn::bwd_dz(d[k], m[k], slope);
+        const int e = (lh * stride + lw) * CH + ln.ci0;
+        lds_store<VEC>(sd + e, d);
+        codes_store<VEC>(sc + e, code);
+      }
+    }
+    __syncthreads();
+    if (ln.in) {
+      const int64_t base = n * g.H * g.W * g.C + ln.c0;
+#pragma unroll 2
+      for (int i = ln.row; i < ph * pw; i += ln.rps) {
+        const int lh = i / pw, lw = i - lh * pw;
+        const bool hb = (lh & 1) && ho0 + (lh >> 1) + 1 < g.Ho, wb = (lw & 1) && wo0 + (lw >> 1) + 1 < g.Wo;
+        const int64_t e = base + ((int64_t)(2 * ho0 + lh) * g.W + (2 * wo0 + lw)) * g.C;
+        float v[VEC], dz[VEC];
+        load<VEC, AL>(x + e, v);
+        pool_rows_dz<VEC>(sd, sc, lh, lw, hb, wb, stride, CH, ln.ci0, dz);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) v[k] = bn::bwd_dx(dz[k], bn::xhat(v[k], nm[k]), bw[k]);
+        store<VEC, AL>(dx + e, v);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+template <bool TRAIN>
+static void launch_pool_fwd(hipStream_t st, const float* x, const float* gamma, const float* beta, int64_t N, int C, int H, int W, float eps,
+                            float momentum, float slope, const float* part, float* P, float* save_mean, float* save_invstd, float* rm,
+                            float* rv) {
+  const PoolRows geo = pool_rows_geometry(N, C, H, W);
+  const Rows& r = geo.rows;
+  const dim3 grid((unsigned)r.chunks, (unsigned)geo.Tf), block(kThreads);
+  with_lane(r.vec, aligned16(x) && aligned16(P), [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((pool_rows_fwd_k<T::VEC, T::AL, TRAIN>), grid, block, 0, st, x, gamma, beta, N * geo.Ho * geo.Wo, C, H, W, geo.Ho,
+                       geo.Wo, r.lpr, r.mg, r.ms, r.S, geo.tile_f, (float)(N * H * W), eps, momentum, slope, part, P, save_mean, save_invstd,
+                       rm, rv);
+  });
+}
+
 }  // namespace nhwc
 }  // namespace bn2d
 }  // namespace clica
@@ -407,6 +708,84 @@ extern "C" int clica_bn2d_nhwc_act_bwd(const float* X, const float* Y, const flo
                        (int)C, geo.lpr, geo.mg, geo.ms, geo.S, geo.tile, (float)M, slope, part, dX, dR, dgamma, dbeta);
   });
   return launch_status("clica_bn2d_nhwc_act_bwd");
+}
+
+#define CLICA_POOL_NHWC_SHAPE(fn, min_M)                                                                                                  \
+  CLICA_CHECK_ARG(N >= 1 && N <= INT32_MAX && bn2d::pool_rows_fits(H, W, C) && (double)N * H * W >= (min_M) &&                            \
+                      (double)N * (double)H * (double)W * (double)C < 1e18,                                                               \
+                  fn ": N=%lld C=%d H=%d W=%d (N >= 1, 1 <= C <= %d, 1 <= H, W <= %d, N H W >= %d)", (long long)N, C, H, W, bn2d::kMaxC,  \
+                  bn2d::kPoolRowsMaxSide, (min_M))
+
+// (as pool2d.hip's: the pool's argmax is taken after the activation)
+#define CLICA_POOL_NHWC_SLOPE(fn) CLICA_CHECK_ARG(slope >= 0.f && slope <= 1.f, fn ": slope=%g must be in [0, 1]", slope)
+
+#define CLICA_POOL_NHWC_WORKSPACE(fn) \
+  CLICA_BN_WORKSPACE(fn, bn2d::pool_rows_workspace_bytes(N, C, H, W), "clica_bn2d_nhwc_maxpool_workspace_bytes", CLICA_E_WORKSPACE)
+
+extern "C" int clica_bn2d_nhwc_maxpool_workspace_bytes(int64_t N, int32_t C, int32_t H, int32_t W, size_t* bytes) {
+  CLICA_CHECK_ARG(bytes != nullptr, "clica_bn2d_nhwc_maxpool_workspace_bytes: bytes is NULL");
+  CLICA_POOL_NHWC_SHAPE("clica_bn2d_nhwc_maxpool_workspace_bytes", 2);
+  *bytes = bn2d::pool_rows_workspace_bytes(N, C, H, W);
+  return CLICA_OK;
+}
+
+extern "C" int clica_bn2d_nhwc_act_maxpool_fwd_train(const float* X, const float* gamma, const float* beta, int64_t N, int32_t C, int32_t H,
+                                                     int32_t W, float eps, float momentum, float slope, float* P, float* save_mean,
+                                                     float* save_invstd, float* running_mean, float* running_var, void* workspace,
+                                                     size_t workspace_bytes, clica_stream_t stream) {
+  CLICA_POOL_NHWC_SHAPE("clica_bn2d_nhwc_act_maxpool_fwd_train", 2);
+  CLICA_POOL_NHWC_SLOPE("clica_bn2d_nhwc_act_maxpool_fwd_train");
+  CLICA_CHECK_ARG(X && gamma && beta && P && save_mean && save_invstd && workspace, "clica_bn2d_nhwc_act_maxpool_fwd_train: NULL pointer");
+  CLICA_POOL_NHWC_WORKSPACE("clica_bn2d_nhwc_act_maxpool_fwd_train");
+  hipStream_t st = as_stream(stream);
+  float* part = static_cast<float*>(workspace);
+  const int64_t M = N * H * W;
+  const bn2d::Rows geo = bn2d::rows_geometry(M, C);          // the unit's statistics launch: its partials, its bits
+  const dim3 grid((unsigned)geo.chunks, (unsigned)geo.S), block(bn2d::kThreads);
+  with_lane(geo.vec, bn2d::aligned16(X), [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((bn2d::nhwc::rows_stats_k<T::VEC, T::AL>), grid, block, 0, st, X, M, (int)C, geo.lpr, geo.per, part);
+  });
+  bn2d::nhwc::launch_pool_fwd<true>(st, X, gamma, beta, N, (int)C, (int)H, (int)W, eps, momentum, slope, part, P, save_mean, save_invstd,
+                                    running_mean, running_var);
+  return launch_status("clica_bn2d_nhwc_act_maxpool_fwd_train");
+}
+
+extern "C" int clica_bn2d_nhwc_act_maxpool_fwd_eval(const float* X, const float* gamma, const float* beta, const float* running_mean,
+                                                    const float* running_var, int64_t N, int32_t C, int32_t H, int32_t W, float eps,
+                                                    float slope, float* P, clica_stream_t stream) {
+  CLICA_POOL_NHWC_SHAPE("clica_bn2d_nhwc_act_maxpool_fwd_eval", 1);
+  CLICA_POOL_NHWC_SLOPE("clica_bn2d_nhwc_act_maxpool_fwd_eval");
+  CLICA_CHECK_ARG(X && gamma && beta && running_mean && running_var && P, "clica_bn2d_nhwc_act_maxpool_fwd_eval: NULL pointer");
+  // (the inference instance only reads the running statistics)
+  bn2d::nhwc::launch_pool_fwd<false>(as_stream(stream), X, gamma, beta, N, (int)C, (int)H, (int)W, eps, 0.f, slope, nullptr, P, nullptr,
+                                     nullptr, const_cast<float*>(running_mean), const_cast<float*>(running_var));
+  return launch_status("clica_bn2d_nhwc_act_maxpool_fwd_eval");
+}
+
+extern "C" int clica_bn2d_nhwc_act_maxpool_bwd(const float* X, const float* dP, const float* gamma, const float* beta, const float* save_mean,
+                                               const float* save_invstd, int64_t N, int32_t C, int32_t H, int32_t W, float slope, float* dX,
+                                               float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, clica_stream_t stream) {
+  CLICA_POOL_NHWC_SHAPE("clica_bn2d_nhwc_act_maxpool_bwd", 2);
+  CLICA_POOL_NHWC_SLOPE("clica_bn2d_nhwc_act_maxpool_bwd");
+  CLICA_CHECK_ARG(X && dP && gamma && beta && save_mean && save_invstd && dX && dgamma && dbeta && workspace,
+                  "clica_bn2d_nhwc_act_maxpool_bwd: NULL pointer");
+  CLICA_POOL_NHWC_WORKSPACE("clica_bn2d_nhwc_act_maxpool_bwd");
+  const bn2d::PoolRows geo = bn2d::pool_rows_geometry(N, C, H, W);
+  const bn2d::Rows& r = geo.rows;
+  const bn2d::nhwc::PoolPlane plane{(int)H, (int)W, (int)C, geo.Ho, geo.Wo, geo.BH, geo.BW, geo.nbh, geo.nbw};
+  const dim3 sgrid((unsigned)r.chunks, (unsigned)geo.Sb), agrid((unsigned)r.chunks, (unsigned)geo.Ta), block(bn2d::kThreads);
+  hipStream_t st = as_stream(stream);
+  float* part = static_cast<float*>(workspace);
+  const bool al = bn2d::aligned16(X) && bn2d::aligned16(dP) && bn2d::aligned16(dX);
+  with_lane(r.vec, al, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((bn2d::nhwc::pool_rows_sums_k<T::VEC, T::AL>), sgrid, block, 0, st, X, dP, gamma, beta, save_mean, save_invstd,
+                       N * geo.Ho * geo.Wo, (int)C, (int)H, (int)W, geo.Ho, geo.Wo, r.lpr, geo.per_b, slope, part);
+    hipLaunchKernelGGL((bn2d::nhwc::pool_rows_bwd_apply_k<T::VEC, T::AL>), agrid, block, 0, st, X, dP, gamma, beta, save_mean, save_invstd,
+                       plane, r.lpr, r.mg, geo.msb, geo.Sb, geo.tiles, geo.per_a, (float)(N * H * W), slope, part, dX, dgamma, dbeta);
+  });
+  return launch_status("clica_bn2d_nhwc_act_maxpool_bwd");
 }
 
 // (the limits of clica_avgpool2d_global_*: pool2d.hip)

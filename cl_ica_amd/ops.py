@@ -1186,7 +1186,7 @@ def avgpool2d_global_bwd_nhwc(dy, H: int, W: int):
     return _avgpool2d_global_bwd(_NHWC, dy, H, W)
 
 
-# ------------------------------------------------------------------------------- the stem unit with its max-pool (NCHW only)
+# ------------------------------------------------------------------------------- the stem unit with its max-pool, contiguous NCHW
 POOL_LDS_FLOATS = 112 * 112 + 56 * 56 + 56 * 56 // 8      # csrc/bn2d.h kPoolLdsFloats: a plane, its window gradients and argmax nibbles in LDS
 
 
@@ -1257,6 +1257,76 @@ def batchnorm2d_act_maxpool_bwd(x, dp, weight, bias, save_mean, save_invstd, slo
     check(load().clica_bn2d_act_maxpool_bwd(x.data_ptr(), dp.data_ptr(), weight.data_ptr(), bias.data_ptr(), save_mean.data_ptr(),
                                             save_invstd.data_ptr(), N, n, H, W, float(slope), dx.data_ptr(), dw.data_ptr(), db.data_ptr(),
                                             ws.data_ptr(), ws.numel(), stream_ptr()), "clica_bn2d_act_maxpool_bwd")
+    return dx, dw, db
+
+
+# ------------------------------------------------------------------------------- the stem unit with its max-pool, channels-last
+POOL_NHWC_MAX_SIDE = 1 << 15               # csrc/bn2d.h kPoolRowsMaxSide
+BN2D_MAX_C = 1 << 20                       # csrc/bn2d.h kMaxC
+
+
+def bn2d_nhwc_maxpool_fits(H: int, W: int, C_: int) -> bool:
+    """Is an H x W plane of C channels within the limits of clica_bn2d_nhwc_act_maxpool_*?  (Its kernels tile the plane: no limit from LDS.)"""
+    return 1 <= H <= POOL_NHWC_MAX_SIDE and 1 <= W <= POOL_NHWC_MAX_SIDE and 1 <= C_ <= BN2D_MAX_C
+
+
+def bn2d_nhwc_maxpool_workspace(N: int, C_: int, H: int, W: int, device) -> torch.Tensor:
+    """The cached workspace of clica_bn2d_nhwc_act_maxpool_fwd_train / _bwd for a channels-last x[N, C, H, W] on `device`."""
+    shape = (int(N), int(C_), int(H), int(W))
+    return _partial_workspace("pool_nhwc", shape, device, "clica_bn2d_nhwc_maxpool_workspace_bytes", shape,
+                              f"bn2d + max-pool (channels-last): no workspace for shape ({N}, {C_}, {H}, {W})")
+
+
+def batchnorm2d_act_maxpool_fwd_nhwc(x, weight, bias, running_mean=None, running_var=None, eps: float = 1e-5, momentum: float = 0.1,
+                                     slope: float = 0.0):
+    """batchnorm2d_act_maxpool_fwd on a dense channels-last x (N H W >= 2): two launches (clica_bn2d_nhwc_act_maxpool_fwd_train).
+    Returns (p [N, C, Ho, Wo] channels-last, save_mean [C], save_invstd [C]); p and the statistics have the bits of
+    batchnorm2d_act_fwd_nhwc followed by max_pool2d(., 3, 2, 1).  Anything but a dense channels-last map and vectors of C values:
+    ValueError, before any launch."""
+    x = _bn2d_nhwc_map("x", x)
+    N, n, H, W = x.shape
+    _running_pair(running_mean, running_var)
+    _norm_vecs(n, weight=weight, bias=bias, running_mean=running_mean, running_var=running_var)
+    _on_gpu(x=x, weight=weight, bias=bias, running_mean=running_mean, running_var=running_var)
+    ws = bn2d_nhwc_maxpool_workspace(N, n, H, W, x.device)       # (validates the shape)
+    p = _NHWC.empty((N, n) + maxpool_out_hw(H, W), x.device)
+    save_mean = torch.empty(n, dtype=torch.float32, device=x.device)
+    save_invstd = torch.empty(n, dtype=torch.float32, device=x.device)
+    check(load().clica_bn2d_nhwc_act_maxpool_fwd_train(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), N, n, H, W, float(eps),
+                                                       float(momentum), float(slope), p.data_ptr(), save_mean.data_ptr(),
+                                                       save_invstd.data_ptr(), ptr(running_mean), ptr(running_var), ws.data_ptr(),
+                                                       ws.numel(), stream_ptr()), "clica_bn2d_nhwc_act_maxpool_fwd_train")
+    return p, save_mean, save_invstd
+
+
+def batchnorm2d_act_maxpool_eval_nhwc(x, weight, bias, running_mean, running_var, eps: float = 1e-5, slope: float = 0.0):
+    """The same on the running statistics (inference): one launch (clica_bn2d_nhwc_act_maxpool_fwd_eval)."""
+    x = _bn2d_nhwc_map("x", x)
+    N, n, H, W = x.shape
+    _norm_vecs(n, weight=weight, bias=bias, running_mean=running_mean, running_var=running_var)
+    _on_gpu(x=x, weight=weight, bias=bias, running_mean=running_mean, running_var=running_var)
+    p = _NHWC.empty((N, n) + maxpool_out_hw(H, W), x.device)
+    check(load().clica_bn2d_nhwc_act_maxpool_fwd_eval(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), running_mean.data_ptr(),
+                                                      running_var.data_ptr(), N, n, H, W, float(eps), float(slope), p.data_ptr(),
+                                                      stream_ptr()), "clica_bn2d_nhwc_act_maxpool_fwd_eval")
+    return p
+
+
+def batchnorm2d_act_maxpool_bwd_nhwc(x, dp, weight, bias, save_mean, save_invstd, slope: float = 0.0):
+    """(dx, dweight, dbias) of batchnorm2d_act_maxpool_fwd_nhwc from its input x, the pooled gradient dp (both dense channels-last) and
+    the saved statistics: two launches (clica_bn2d_nhwc_act_maxpool_bwd).  dx is channels-last."""
+    x = _bn2d_nhwc_map("x", x)
+    N, n, H, W = x.shape
+    _bn2d_nhwc_map("dp", dp, (N, n) + maxpool_out_hw(H, W))
+    _norm_vecs(n, weight=weight, bias=bias, save_mean=save_mean, save_invstd=save_invstd)
+    _on_gpu(x=x, dp=dp, weight=weight, bias=bias, save_mean=save_mean, save_invstd=save_invstd)
+    ws = bn2d_nhwc_maxpool_workspace(N, n, H, W, x.device)
+    dx = _NHWC.empty(x.shape, x.device)
+    dw = torch.empty(n, dtype=torch.float32, device=x.device)
+    db = torch.empty(n, dtype=torch.float32, device=x.device)
+    check(load().clica_bn2d_nhwc_act_maxpool_bwd(x.data_ptr(), dp.data_ptr(), weight.data_ptr(), bias.data_ptr(), save_mean.data_ptr(),
+                                                 save_invstd.data_ptr(), N, n, H, W, float(slope), dx.data_ptr(), dw.data_ptr(),
+                                                 db.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()), "clica_bn2d_nhwc_act_maxpool_bwd")
     return dx, dw, db
 
 

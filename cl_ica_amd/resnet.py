@@ -21,11 +21,15 @@ unit that never writes the 32 x 32 activation, pooling indices or their sparse g
 With NHWC_MODE "hip" (and NORM_MODE "hip") a dense channels-last input -- ``model.to(memory_format=torch.channels_last)`` -- takes the
 same units on the kernels of csrc/bn2d_nhwc.hip, whose outputs and gradients are channels-last again, so the backbone stays NHWC between
 MIOpen's convolutions; the average pool follows under POOL_MODE "hip".  A residual in the other layout runs torch's path (no hidden
-copy), and the stem's max-pool is the unit followed by ``nn.MaxPool2d`` (the fused stem kernel holds NCHW planes in LDS).  The default
-is "torch": channels-last inputs run the modules' own forward, as they always did.
+copy).  The default is "torch": channels-last inputs run the modules' own forward, as they always did.
 
-Both layouts share the code here: ``_layout(x)`` names the layout once per unit, and ``_unit``, ``_BN2dActFn`` and ``_GlobalAvgPoolFn``
-take it as an argument that picks the ``ops`` function (``name`` or ``name_nhwc``) and the memory format of the incoming gradient.
+The channels-last stem is the unit followed by ``nn.MaxPool2d`` unless NHWC_STEM_MODE is "hip" (with NORM_MODE, POOL_MODE and NHWC_MODE
+all "hip"): then ``bn1 + relu + maxpool`` is the fused stem unit of csrc/bn2d_nhwc.hip, which tiles the plane instead of holding it in
+LDS and, as the NCHW one, writes neither the activation nor indices.  Its default is "torch".
+
+Both layouts share the code here: ``_layout(x)`` names the layout once per unit, and ``_unit``, ``_stem``, ``_BN2dActFn``,
+``_BN2dActPoolFn`` and ``_GlobalAvgPoolFn`` take it as an argument that picks the ``ops`` function (``name`` or ``name_nhwc``) and the
+memory format of the incoming gradient.
 """
 from __future__ import annotations
 
@@ -55,6 +59,12 @@ if POOL_MODE not in ("hip", "torch"):
 NHWC_MODE = os.environ.get("CLICA_RESNET_NHWC", "torch")
 if NHWC_MODE not in ("hip", "torch"):
     raise ValueError(f"CLICA_RESNET_NHWC={NHWC_MODE!r} (one of 'hip', 'torch')")
+
+# "hip": a channels-last stem runs bn1 + relu + maxpool as the fused unit of csrc/bn2d_nhwc.hip, where NORM_MODE, POOL_MODE and NHWC_MODE
+# are all "hip" and it applies; "torch": the bn2d unit followed by nn.MaxPool2d, as before.  Read at call time.
+NHWC_STEM_MODE = os.environ.get("CLICA_RESNET_NHWC_STEM", "torch")
+if NHWC_STEM_MODE not in ("hip", "torch"):
+    raise ValueError(f"CLICA_RESNET_NHWC_STEM={NHWC_STEM_MODE!r} (one of 'hip', 'torch')")
 
 _NHWC = torch.channels_last
 # A layout ("nchw" / "nhwc", what _layout gives) picks the memory format of a gradient and the ops function of a name, looked up on the
@@ -89,23 +99,25 @@ class _BN2dActFn(torch.autograd.Function):
 
 
 class _BN2dActPoolFn(torch.autograd.Function):
-    """The stem: nn.BatchNorm2d in training mode + ReLU + nn.MaxPool2d(3, 2, 1) on clica_bn2d_act_maxpool_fwd_train / _bwd.  The backward
-    recomputes the activation from x, so nothing of its size is saved but x itself."""
+    """The stem: nn.BatchNorm2d in training mode + ReLU + nn.MaxPool2d(3, 2, 1) on clica_bn2d_act_maxpool_fwd_train / _bwd or, for `layout`
+    "nhwc" (a dense channels-last x; output and input gradient channels-last again), on clica_bn2d_nhwc_act_maxpool_fwd_train / _bwd.  The
+    backward recomputes the activation from x, so nothing of its size is saved but x itself."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, mod, slope):
-        p, save_mean, save_invstd = ops.batchnorm2d_act_maxpool_fwd(x, weight, bias, mod.running_mean, mod.running_var, mod.eps,
-                                                                    mod.momentum, slope)
+    def forward(ctx, x, weight, bias, mod, slope, layout):
+        p, save_mean, save_invstd = _op("batchnorm2d_act_maxpool_fwd", layout)(x, weight, bias, mod.running_mean, mod.running_var, mod.eps,
+                                                                               mod.momentum, slope)
         ctx.save_for_backward(x, weight, bias, save_mean, save_invstd)
-        ctx.slope = slope
+        ctx.slope, ctx.layout = slope, layout
         return p
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gp):
         x, weight, bias, save_mean, save_invstd = ctx.saved_tensors
-        dx, dw, db = ops.batchnorm2d_act_maxpool_bwd(x, gp.contiguous(), weight, bias, save_mean, save_invstd, ctx.slope)
-        return dx, dw, db, None, None
+        dx, dw, db = _op("batchnorm2d_act_maxpool_bwd", ctx.layout)(x, gp.contiguous(memory_format=_FORMAT[ctx.layout]), weight, bias,
+                                                                    save_mean, save_invstd, ctx.slope)
+        return dx, dw, db, None, None, None
 
 
 class _GlobalAvgPoolFn(torch.autograd.Function):
@@ -176,12 +188,15 @@ def _unit(bn, relu, x, r=None):
 
 def _stem_pool_on_hip(bn, pool, x) -> bool:
     """Does the fused stem unit cover bn + relu + `pool` on this input?  Otherwise: the unfused unit, then the module."""
-    if POOL_MODE != "hip" or _layout(x) != "nchw" or not _bn2d_on_hip(bn, x, "nchw"):      # (the fused stem kernel holds NCHW planes in LDS)
+    layout = _layout(x)
+    if POOL_MODE != "hip" or (layout == "nhwc" and NHWC_STEM_MODE != "hip") or not _bn2d_on_hip(bn, x, layout):
         return False
     one = lambda v, k: v == k or v == (k, k)
     if not (type(pool) is nn.MaxPool2d and one(pool.kernel_size, 3) and one(pool.stride, 2) and one(pool.padding, 1) and one(pool.dilation, 1)
             and not pool.ceil_mode and not pool.return_indices):
         return False
+    if layout == "nhwc":
+        return ops.bn2d_nhwc_maxpool_fits(x.shape[2], x.shape[3], x.shape[1])
     return ops.bn2d_maxpool_fits(x.shape[2], x.shape[3])
 
 
@@ -189,11 +204,13 @@ def _stem(bn, relu, pool, x):
     """pool(relu(bn(x))) as one fused call where the kernels apply."""
     if not _stem_pool_on_hip(bn, pool, x):
         return pool(_unit(bn, relu, x))
+    layout = _layout(x)
     if bn.training:
-        ops.bn2d_maxpool_workspace(x.shape[0], x.shape[1], x.shape[2], x.shape[3], x.device)      # (raises while capturing without a warm-up)
+        workspace = ops.bn2d_maxpool_workspace if layout == "nchw" else ops.bn2d_nhwc_maxpool_workspace
+        workspace(x.shape[0], x.shape[1], x.shape[2], x.shape[3], x.device)      # (raises while capturing without a warm-up)
         bn.num_batches_tracked.add_(1)
-        return _BN2dActPoolFn.apply(x, bn.weight, bn.bias, bn, 0.0)
-    return ops.batchnorm2d_act_maxpool_eval(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.eps), 0.0)
+        return _BN2dActPoolFn.apply(x, bn.weight, bn.bias, bn, 0.0, layout)
+    return _op("batchnorm2d_act_maxpool_eval", layout)(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.eps), 0.0)
 
 
 def _avgpool_on_hip(pool, x) -> bool:

@@ -774,6 +774,35 @@ int clica_bn2d_nhwc_act_bwd(const float* X, const float* Y, const float* dY, con
                             const float* save_invstd, int64_t M, int32_t C, float slope, float* dX, float* dR /*or NULL*/, float* dgamma,
                             float* dbeta, void* workspace, size_t workspace_bytes, clica_stream_t stream);
 
+/* The stem unit with its max-pool on DENSE CHANNELS-LAST fp32 X[N, H, W, C] (csrc/bn2d_nhwc.hip):
+ *   P[N, Ho, Wo, C] = maxpool 3 x 3 / stride 2 / padding 1 (floor mode) of lrelu(gamma xhat + beta, slope),
+ * channels-last again, as is dX.  Mathematics, arguments, rules and return codes are those of clica_bn2d_act_maxpool_* above: slope in
+ * [0, 1], N H W >= 2 in training, a NULL pointer or a shape outside the contract CLICA_E_INVALID before any launch, a short workspace
+ * CLICA_E_WORKSPACE.  The activation, pooling indices and the sparse gradient are never written.
+ * Training forward: the statistics launch of clica_bn2d_nhwc_act_fwd_train, then one launch that merges its partials as that unit's
+ * apply launch does (one workgroup per chunk of channels writes save_mean, save_invstd and the running statistics), forms y with the
+ * unit's element functions for the <= 9 inputs of an output pixel and writes the first maximum in scan order: P and the statistics carry
+ * the bits of clica_bn2d_nhwc_act_fwd_train followed by torch's max_pool2d, signed zeros included.  Inference: one launch on the running
+ * statistics.  Backward from X, dP, gamma, BETA and the saved statistics, two launches (partials [Sb][C] of sum dZ and sum dZ xhat, then
+ * their merge in split order and dX); both recompute y and each window's first maximum (rows, then columns, strict >) per tile =
+ * (image, band of output rows, band of output columns, chunk of channels), and a pixel gathers dZ from the <= 4 windows whose first
+ * maximum it is, in window order.  The lanes are those of the unit (4 consecutive channels when C % 4 == 0, else 1; 16-byte accesses
+ * when X, dP, P / dX are all 16-byte aligned, else scalar accesses of the same values in the same order: the same bits).  LDS holds 5
+ * bytes per (window, channel) of a tile of at most 9 window columns, never a plane: the limits are 1 <= H, W <= 32768, 1 <= C <= 2^20.
+ * All element offsets are 64-bit.  No floating-point atomics, no in-kernel counters: eager launches and graph replays give the same
+ * bits.  clica_bn2d_nhwc_maxpool_workspace_bytes is host-only: -1 for N H W < 2, C < 1, H or W outside the limits, bytes == NULL. */
+int clica_bn2d_nhwc_maxpool_workspace_bytes(int64_t N, int32_t C, int32_t H, int32_t W, size_t* bytes);
+int clica_bn2d_nhwc_act_maxpool_fwd_train(const float* X, const float* gamma, const float* beta, int64_t N, int32_t C, int32_t H, int32_t W,
+                                          float eps, float momentum, float slope, float* P, float* save_mean, float* save_invstd,
+                                          float* running_mean /*[C] or NULL*/, float* running_var /*[C] or NULL*/, void* workspace,
+                                          size_t workspace_bytes, clica_stream_t stream);
+int clica_bn2d_nhwc_act_maxpool_fwd_eval(const float* X, const float* gamma, const float* beta, const float* running_mean,
+                                         const float* running_var, int64_t N, int32_t C, int32_t H, int32_t W, float eps, float slope,
+                                         float* P, clica_stream_t stream);
+int clica_bn2d_nhwc_act_maxpool_bwd(const float* X, const float* dP, const float* gamma, const float* beta, const float* save_mean,
+                                    const float* save_invstd, int64_t N, int32_t C, int32_t H, int32_t W, float slope, float* dX,
+                                    float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, clica_stream_t stream);
+
 /* Global average pool of dense channels-last fp32 X[N, HW, C]: Y[n, c] = (X[n, 0, c] + X[n, 1, c] + ... in pixel order) x (1 / HW), a
  * thread per (n, c) with the lanes along C, and its backward dX[n, k, c] = dY[n, c] x (1 / HW).  One launch each.
  * 1 <= HW <= 16384, 1 <= C <= 2^20, N >= 1. */

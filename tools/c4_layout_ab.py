@@ -4,12 +4,15 @@
     (a) nchw        contiguous model and inputs: bench.py's own leg, the baseline
     (b) nhwc-torch  channels_last model and inputs, CLICA_RESNET_NHWC=torch: torch's / MIOpen's own BatchNorm, ReLU, add
     (c) nhwc-hip    channels_last model and inputs, CLICA_RESNET_NHWC=hip: the units of csrc/bn2d_nhwc.hip
+    (d) nhwc-hip-stem  as (c) with CLICA_RESNET_NHWC_STEM=hip: the stem's bn1 + relu + maxpool as the fused unit of csrc/bn2d_nhwc.hip
 
   python tools/c4_layout_ab.py                      a throw-away run of every leg (MIOpen's find step), then two rounds alternating the
                                                     legs; each figure the median of three 20-step windows after 6 warm-up steps
+  python tools/c4_layout_ab.py --legs nchw,nhwc-hip,nhwc-hip-stem       the same with these legs only
   python tools/c4_layout_ab.py --leg nhwc-hip       one leg alone, 6 + 30 steps: the program for `rocprofv3 --kernel-trace --stats -- ...`
   python tools/c4_layout_ab.py --units              the fused unit alone per ResNet-18 (M, C) at N = 1024, NHWC against NCHW, event-timed
-                                                    calls (forward = statistics + apply, backward = sums + backward apply) and TB/s
+                                                    calls (forward = statistics + apply, backward = sums + backward apply) and TB/s;
+                                                    then the stem with its max-pool, fused, in both layouts
   python tools/c4_layout_ab.py --summarise T.csv    buckets and per-(kernel, grid) rows of a rocprofv3 *_kernel_trace.csv (no GPU)
 Every mode prints JSON lines; --out FILE also appends them there."""
 import argparse
@@ -22,7 +25,9 @@ import types
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-LEGS = {"nchw": ("contiguous", "torch"), "nhwc-torch": ("channels_last", "torch"), "nhwc-hip": ("channels_last", "hip")}
+# leg -> (memory format, NHWC_MODE, NHWC_STEM_MODE)
+LEGS = {"nchw": ("contiguous", "torch", "torch"), "nhwc-torch": ("channels_last", "torch", "torch"),
+        "nhwc-hip": ("channels_last", "hip", "torch"), "nhwc-hip-stem": ("channels_last", "hip", "hip")}
 # ResNet-18's units at N = 1024 on 64 x 64 images: (name, N, C, H, W, units with / without a residual per view)
 UNIT_SHAPES = [("stem", 1024, 64, 32, 32), ("layer 1", 1024, 64, 16, 16), ("layer 2", 1024, 128, 8, 8), ("layer 3", 1024, 256, 4, 4),
                ("layer 4", 1024, 512, 2, 2)]
@@ -41,7 +46,7 @@ def make_leg(leg):
     import torch
     from cl_ica_amd import resnet, threedident as T
     from cl_ica_amd.optim import Adam
-    fmt_name, nhwc_mode = LEGS[leg]
+    fmt_name, nhwc_mode, stem_mode = LEGS[leg]
     fmt = getattr(torch, fmt_name + "_format" if fmt_name == "contiguous" else fmt_name)
     dev = torch.device("cuda")
     torch.manual_seed(0)
@@ -57,7 +62,7 @@ def make_leg(leg):
     x1 = x1.contiguous(memory_format=fmt)
 
     def step():
-        resnet.NHWC_MODE = nhwc_mode            # (read at call time)
+        resnet.NHWC_MODE, resnet.NHWC_STEM_MODE = nhwc_mode, stem_mode            # (read at call time)
         return T.train_step(((None, None), (x1, x2)), loss, opt, f, sync=False)[0]
     return step
 
@@ -123,9 +128,46 @@ def units(out, reps=20):
             torch.cuda.empty_cache()
 
 
+def stem_units(out, reps=20):
+    """The fused stem unit (bn1 + relu + max-pool 3/2/1) alone at ResNet-18's stem shape, both layouts.  E = N C H W x 4 bytes of x,
+    E / 4 of P and dP; algorithmic bytes: forward x read twice (statistics, pool) + P = 2.25 E; backward x and dP read twice (sums,
+    backward apply) + dx = 3.5 E."""
+    import torch
+    from cl_ica_amd import ops
+    dev = torch.device("cuda")
+    name, N, C, H, W = UNIT_SHAPES[0]
+    E = N * C * H * W * 4
+    w = torch.ones(C, device=dev); b = torch.zeros(C, device=dev)
+    for layout in ("nchw", "nhwc"):
+        fmt = torch.channels_last if layout == "nhwc" else torch.contiguous_format
+        sfx = "_nhwc" if layout == "nhwc" else ""
+        fwd, bwd, ev = (getattr(ops, "batchnorm2d_act_maxpool_" + k + sfx) for k in ("fwd", "bwd", "eval"))
+        x = torch.randn(N, C, H, W, device=dev).contiguous(memory_format=fmt)
+        p, m, i = fwd(x, w, b, None, None, 1e-5, 0.1, 0.0)
+        dp = torch.randn(*p.shape, device=dev).contiguous(memory_format=fmt)
+        calls = {"forward (statistics + pool)": (lambda: fwd(x, w, b, None, None, 1e-5, 0.1, 0.0), 2.25 * E),
+                 "backward (sums + backward apply)": (lambda: bwd(x, dp, w, b, m, i, 0.0), 3.5 * E),
+                 "inference pool": (lambda: ev(x, w, b, m, i.reciprocal().square(), 1e-5, 0.0), 1.25 * E)}
+        for what, (call, nbytes) in calls.items():
+            for _ in range(3):
+                call()
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                call()
+            e1.record()
+            torch.cuda.synchronize()
+            us = e0.elapsed_time(e1) * 1e3 / reps
+            emit(out, {"unit": "stem + max-pool", "M": N * H * W, "C": C, "E_MB": round(E / 1e6, 1), "layout": layout, "call": what,
+                       "us_per_call": round(us, 1), "TB_per_s": round(nbytes / us / 1e6, 2)})
+        del x, p, dp
+        torch.cuda.empty_cache()
+
+
 def bucket_of(name):
     n = name
-    if "clica::bn2d::nhwc::avgpool" in n or "clica::avgpool" in n or "clica::bn2d::pool_" in n:
+    if "clica::bn2d::nhwc::avgpool" in n or "clica::bn2d::nhwc::pool_" in n or "clica::avgpool" in n or "clica::bn2d::pool_" in n:
         return "clica pool kernels"
     if "clica::bn2d::nhwc" in n:
         return "clica::bn2d::nhwc::* units"
@@ -179,6 +221,7 @@ def summarise(path, out, top=45):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--leg", choices=sorted(LEGS), help="run this leg alone (for a profiler)")
+    ap.add_argument("--legs", default=None, help="comma-separated legs of the alternating run (default: all)")
     ap.add_argument("--units", action="store_true")
     ap.add_argument("--summarise", metavar="KERNEL_TRACE_CSV")
     ap.add_argument("--steps", type=int, default=None)
@@ -192,13 +235,17 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("c4_layout_ab.py measures on the GPU: none here")
     if args.units:
-        return units(args.out)
+        units(args.out)
+        return stem_units(args.out)
     if args.leg:
         return emit(args.out, dict(run_leg(args.leg, args.steps or 30, args.warmup, 1), run="alone"))
-    for leg in LEGS:                                   # MIOpen's find step of every leg, outside every window
+    legs = args.legs.split(",") if args.legs else list(LEGS)
+    if any(leg not in LEGS for leg in legs):
+        raise SystemExit(f"--legs {args.legs!r}: legs are {sorted(LEGS)}")
+    for leg in legs:                                   # MIOpen's find step of every leg, outside every window
         emit(args.out, dict(run_leg(leg, 4, 2, 1), run="throw-away"))
     for rnd in range(1, args.rounds + 1):
-        for leg in LEGS:
+        for leg in legs:
             emit(args.out, dict(run_leg(leg, args.steps or 20, args.warmup, 3), run=f"round {rnd}"))
 
 
