@@ -668,6 +668,30 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, step_dev, lr, beta1=0.9, beta2=0
                                           step_dev.data_ptr(), ticket.data_ptr(), stream_ptr()), "clica_adam_step_tick")
 
 
+def sgd_step(param, grad, momentum_buf, step_dev, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, maximize=False,
+             grad_scale=1.0, ticket: Optional[torch.Tensor] = None, count: Optional[int] = None):
+    """In-place torch.optim.SGD update on the first `count` (default: all) elements of flat fp32 arenas; `step_dev` int32[1] = updates
+    already applied (0: the momentum buffer takes the gradient as it is).  `momentum_buf` may be None when momentum == 0.  With `ticket` (device int32[1], zero) the same launch also
+    advances `step_dev` by one (clica_sgd_step_tick)."""
+    global PARAM_EPOCH
+    PARAM_EPOCH += 1
+    for nm, t in (("param", param), ("grad", grad), ("momentum_buf", momentum_buf)):
+        if t is None and nm == "momentum_buf":
+            continue
+        require_cuda(t, nm)
+        if not t.is_contiguous():
+            raise ValueError(f"{nm} must be contiguous")
+    count = param.numel() if count is None else int(count)
+    if count > min(t.numel() for t in (param, grad, momentum_buf) if t is not None):
+        raise ValueError("sgd_step: an arena is shorter than count")
+    args = (param.data_ptr(), grad.data_ptr(), ptr(momentum_buf), count, float(lr), float(momentum), float(dampening),
+            float(weight_decay), int(bool(nesterov)), int(bool(maximize)), float(grad_scale), step_dev.data_ptr())
+    if ticket is None:
+        check(load().clica_sgd_step(*args, stream_ptr()), "clica_sgd_step")
+    else:
+        check(load().clica_sgd_step_tick(*args, ticket.data_ptr(), stream_ptr()), "clica_sgd_step_tick")
+
+
 def publish_host(src: torch.Tensor, host_dst: torch.Tensor, seq_dev: torch.Tensor, host_seq: torch.Tensor):
     """src (device fp32, <= 64 values) -> host_dst (pinned fp32), then ++seq_dev (device int32) -> host_seq (pinned int32) behind a
     system-scope release: a host read from the middle of a captured step (clica_publish_host)."""

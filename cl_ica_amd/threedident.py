@@ -21,7 +21,7 @@ from typing import Callable, Optional
 import torch
 from torch import nn
 
-from . import layers, lazy, losses, ops
+from . import encoders, layers, lazy, losses, ops
 from .encoders import _MLPStackFn
 
 __all__ = ["setup_f", "make_unsupervised_loss", "train_step", "HipLinear", "unpack_item_list", "make_supervised_loss",
@@ -68,6 +68,10 @@ def setup_f(args, n_non_angular_latents: int, n_angular_latents: int,
         return nn.Sequential(layers.Flatten())
     n_latents = n_non_angular_latents + n_angular_latents
     rescaling = make_rescaling(args, n_non_angular_latents, n_angular_latents)
+    if getattr(args, "dummy_mixing", False):      # the encoder of main_mlp on the mixed latents instead of a backbone on images (:348-364)
+        n = n_latents
+        return nn.Sequential(encoders.get_mlp(n_in=n, n_out=n, layers=[n * 10, n * 50, n * 50, n * 50, n * 50, n * 10],
+                                              output_normalization=None), rescaling)
     if base_encoder is None:
         try:
             from torchvision import models       # not in this image; present in the reference's environment

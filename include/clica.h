@@ -1026,6 +1026,41 @@ int clica_adam_step_tick(float* param, const float* grad, float* exp_avg, float*
 int clica_adam_step_s16_tick(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t count,
                              float lr, float beta1, float beta2, float eps, float grad_scale,
                              int32_t* step_dev, int32_t* ticket, void* split16_state, int32_t n_layers, clica_stream_t stream);
+/* ------------------------------------------------------------------------------------
+ * SGD  --  torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov, maximize), the
+ * `--optimizer sgd` of main_3dident.py:453-454, over one flat parameter arena.  `step_dev` is
+ * a device int32 holding the number of updates already applied, t; it only tells the first
+ * update (t == 0: the momentum buffer takes the gradient as it is) from the later ones.  The
+ * call leaves *step_dev unchanged (advance it with clica_tick, or use the _tick variant).
+ * Per element, every line ONE correctly rounded fp32 operation -- multiplies, adds and one
+ * subtraction, no fused multiply-add -- in this order (s = grad_scale, all scalars fp32):
+ *     gr  = g * s
+ *     gr  = -gr                                   (maximize; exact)
+ *     wp  = weight_decay * p ;  gr = gr + wp      (only if weight_decay != 0)
+ *   momentum != 0:
+ *     t == 0:   buf = gr
+ *     t  > 0:   a = momentum * buf ;  b = (1 - dampening) * gr ;  buf = a + b
+ *               ((1 - dampening) is formed once, on the host, as the fp32 difference 1.f - dampening)
+ *     nesterov: c = momentum * buf ;  d = gr + c          otherwise d = buf
+ *   momentum == 0:
+ *     d = gr                                      (momentum_buf is not touched and may be NULL)
+ *     u = lr * d ;  p = p - u
+ * A NumPy float32 restatement of these lines is the kernel's exact expectation (bit for bit).
+ * It is NOT bit-equal to torch's float32 CPU update, which fuses some of the pairs; both are
+ * within a few ulp of the fp64 update.
+ * `count` > 0 elements; the arenas 16-byte aligned; momentum != 0 needs momentum_buf; nesterov
+ * needs momentum != 0 and dampening == 0 (torch raises for these too); otherwise CLICA_E_INVALID.
+ * HBM traffic: 8 B read + 4 B written per parameter, 12 B + 8 B with a momentum buffer (the
+ * first update does not read the buffer).
+ * ---------------------------------------------------------------------------------- */
+int clica_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t count, float lr, float momentum, float dampening,
+                   float weight_decay, int32_t nesterov, int32_t maximize, float grad_scale, const int32_t* step_dev,
+                   clica_stream_t stream);
+/* Same update, and the LAST workgroup to finish advances *step_dev by one, as clica_adam_step_tick (`ticket`: a device int32 owned by
+ * the caller, zero before the first call; the kernel leaves it at zero), so the step replays in a captured graph. */
+int clica_sgd_step_tick(float* param, const float* grad, float* momentum_buf, int64_t count, float lr, float momentum, float dampening,
+                        float weight_decay, int32_t nesterov, int32_t maximize, float grad_scale, int32_t* step_dev, int32_t* ticket,
+                        clica_stream_t stream);
 /* *counter += 1 (single-thread kernel; keeps step/RNG counters on device for graph replay) */
 int clica_tick(int32_t* counter, clica_stream_t stream);
 /* Host reads from the MIDDLE of a captured step (cl_ica_amd/graphed.py: the reference's train_step reads three loss scalars per step,
