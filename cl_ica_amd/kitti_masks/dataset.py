@@ -9,7 +9,8 @@ device tensors for a whole batch, and ONE launch (``clica_kitti_gather_pairs``, 
 and labels -- no workers, no H2D copy per step.  What is kept: ``KittiMasks(path, transform, max_delta_t)`` with ``__len__`` /
 ``__getitem__`` (host arrays, like the reference, for the evaluation code that calls them), ``custom_collate``, and
 ``return_data(args)`` -> an iterable of ``(images, labels)`` batches with the reference's semantics (``batch_size`` halved for
-the pairs, shuffled without replacement every epoch, ``drop_last``).
+the pairs, shuffled without replacement every epoch, ``drop_last``).  ``StreamPairSampler`` / ``return_stream_sampler(args)`` give the
+same stream with the draw inside the gather launch (``clica_kitti_sample_pairs``), for a training step captured with its data.
 
 Out of scope: the ``transform="default"`` augmentation (PIL / torchvision RandomAffine, never enabled by ``return_data``) and the
 download of ``kitti_peds_v2.pickle`` (no network): pass ``data=`` (the unpickled dict) or put the file under ``path``.
@@ -27,7 +28,7 @@ import torch
 
 from .. import ops
 
-__all__ = ["KittiMasks", "custom_collate", "return_data", "DevicePairLoader"]
+__all__ = ["KittiMasks", "custom_collate", "return_data", "DevicePairLoader", "StreamPairSampler", "return_stream_sampler"]
 
 
 class KittiMasks:
@@ -73,6 +74,13 @@ class KittiMasks:
         end = torch.minimum(start + t, self.seq_len[seq] - 1)
         base = self.seq_start[seq]
         return base + start, base + end
+
+    def first_frame_ids(self, index) -> np.ndarray:
+        """Global frame ids of the FIRST frames of the items `index` (host int64 array; the time step does not enter)."""
+        index = np.asarray(index, np.int64)
+        seq = np.searchsorted(self.cumlens, index, side="right")
+        prev = np.where(seq > 0, self.cumlens[np.maximum(seq - 1, 0)], 0)
+        return (self._seq_start_h[seq] + index - prev).astype(np.int64)
 
     def batch(self, index: torch.Tensor, t_steps_forward: torch.Tensor):
         """custom_collate([self[i] for i in index]) with the given time steps: ``(images (2B, 1, H, W), labels (2B, 3))`` on the device."""
@@ -139,12 +147,101 @@ class DevicePairLoader:
             yield self.dataset.batch(idx, self.dataset.sample_time_steps(idx.numel(), self.generator))
 
 
-def return_data(args, data: Optional[dict] = None):
-    """dataset.py:145-175: ``args.batch_size`` counts IMAGES; the loader works on ``batch_size // 2`` pairs."""
+class StreamPairSampler:
+    """The training stream of ``DataLoader(shuffle=True, drop_last=True, collate_fn=custom_collate)`` with the draw on the device: ONE
+    launch per batch (``clica_kitti_sample_pairs``) picks the batch's start items from the epoch's permutation, draws the time steps,
+    does the index arithmetic of ``__getitem__`` and gathers the interleaved pairs -- so the launch can sit inside a captured training
+    step (``Solver.capture_stream``) and consecutive replays walk the stream with no host write.
+
+    The sampler owns ``order`` (int64 [len(dataset)], the current epoch's permutation), ``state`` (int64 [2]: the device batch counter
+    and the kernel's ticket word) and ``issued``, the host count of draws.  EVERY draw goes through the sampler, so that ``issued``
+    equals the device counter: ``draw_into`` / ``draw`` for an eager launch, ``replayed()`` once per replay of a graph that holds a
+    captured ``draw_into``.  Before the first draw of every epoch (``issued`` a multiple of ``steps_per_epoch``) ``order`` is refilled in
+    place, on the current stream, by ``torch.randperm(out=order)`` from a device generator seeded by `seed`; its address never changes.
+    The stream is a function of `seed` alone: the permutations come from that generator, the time steps from the library's Philox keyed
+    by (seed, pair, batch counter)."""
+
+    def __init__(self, dataset: KittiMasks, pairs_per_batch: int, seed: Optional[int] = None):
+        self.dataset, self.pairs = dataset, int(pairs_per_batch)
+        n = len(dataset)
+        if not 1 <= self.pairs <= n:
+            raise ValueError(f"StreamPairSampler: {self.pairs} pairs per batch from {n} items (no full batch exists)")
+        self.seed = 0 if seed is None else int(seed)
+        self.steps_per_epoch = n // self.pairs
+        dev = dataset.device
+        self.generator = torch.Generator(device=dev)
+        self.generator.manual_seed(self.seed)
+        self.order = torch.empty(n, dtype=torch.int64, device=dev)
+        self.state = torch.zeros(2, dtype=torch.int64, device=dev)
+        self._drawn = torch.zeros((4, self.pairs), dtype=torch.int64, device=dev)
+        self.issued = 0
+        self._epoch_filled = -1
+        self.batch_size = self.pairs
+        self.image_shape = (2 * self.pairs, 1) + tuple(dataset.frames.shape[1:])
+        self.label_shape = (2 * self.pairs, dataset.frame_latents.shape[1])
+
+    def __len__(self):
+        return self.steps_per_epoch
+
+    def prepare(self):
+        """Refill ``order`` if the next draw opens an epoch (idempotent).  A graph owner calls it before capturing ``draw_into``."""
+        epoch = self.issued // self.steps_per_epoch
+        if epoch != self._epoch_filled:
+            torch.randperm(self.order.numel(), out=self.order, generator=self.generator)
+            self._epoch_filled = epoch
+
+    def _launch(self, images, labels):
+        d = self.dataset
+        ops.kitti_sample_pairs(d.frames, d.frame_latents if labels is not None else None, d.cumlens_dev, d.seq_start, d.seq_len, self.order,
+                               self.pairs, d.max_delta_t, self.seed, self.state, images, labels, self._drawn)
+
+    def draw_into(self, images: torch.Tensor, labels: Optional[torch.Tensor] = None):
+        """One launch: the next batch into the caller's static buffers (float32 ``image_shape`` / ``label_shape``).  Under stream capture
+        the launch is recorded and nothing is counted: the graph's owner calls ``replayed()`` per replay."""
+        if torch.cuda.is_current_stream_capturing():
+            if self._epoch_filled != self.issued // self.steps_per_epoch:
+                raise RuntimeError("StreamPairSampler.draw_into under capture: call prepare() before the capture begins")
+            self._launch(images, labels)
+            return
+        self.prepare()
+        self._launch(images, labels)
+        self.issued += 1
+
+    def draw(self):
+        images = torch.empty(self.image_shape, dtype=torch.float32, device=self.dataset.device)
+        labels = torch.empty(self.label_shape, dtype=torch.float32, device=self.dataset.device)
+        self.draw_into(images, labels)
+        return images, labels
+
+    def replayed(self):
+        """A graph holding one captured ``draw_into`` was just replayed on the current stream: count the draw and, at an epoch boundary,
+        refill ``order`` behind it (stream order puts the refill after the replay's reads and before the next replay's)."""
+        self.issued += 1
+        self.prepare()
+
+    def last_draw(self):
+        """(index, t, first frame, second frame) of the most recent launch: int64 [pairs] each, copies."""
+        return tuple(self._drawn.clone().unbind(0))
+
+    def __iter__(self):
+        for _ in range(len(self)):
+            yield self.draw()
+
+
+def _train_set(args, data):
     assert args.image_size == 64, "currently only image size of 64 is supported"
     assert not (args.batch_size % 2)
     if args.dataset.lower() != "kittimasks":
         raise NotImplementedError
-    train_data = KittiMasks(max_delta_t=args.kitti_max_delta_t, transform=None, data=data,
-                            **({"path": args.dset_dir} if getattr(args, "dset_dir", None) else {}))
-    return DevicePairLoader(train_data, args.batch_size // 2, shuffle=True, drop_last=True, seed=getattr(args, "seed", None))
+    return KittiMasks(max_delta_t=args.kitti_max_delta_t, transform=None, data=data,
+                      **({"path": args.dset_dir} if getattr(args, "dset_dir", None) else {}))
+
+
+def return_data(args, data: Optional[dict] = None):
+    """dataset.py:145-175: ``args.batch_size`` counts IMAGES; the loader works on ``batch_size // 2`` pairs."""
+    return DevicePairLoader(_train_set(args, data), args.batch_size // 2, shuffle=True, drop_last=True, seed=getattr(args, "seed", None))
+
+
+def return_stream_sampler(args, data: Optional[dict] = None):
+    """``return_data`` with the draw inside the gather launch: same argument rules, a ``StreamPairSampler`` over the same data set."""
+    return StreamPairSampler(_train_set(args, data), args.batch_size // 2, seed=getattr(args, "seed", None))

@@ -7,7 +7,8 @@ checkpoints in the ``{iter, model_states, optim_states}`` layout), ``save_checkp
 The per-batch arithmetic (:61-74) lives in ``train_iteration``: ``mu = net(x)``, the strided views ``mu[::2]`` /
 ``mu[1::2]`` go to ``LpSimCLRLoss(p, tau=1, compat)`` without copies, negatives are the rolled first views, then
 ``zero_grad / backward / step`` on the flat-arena Adam (one launch).  The encoder's convolutions are the hand-written stack of
-``cl_ica_amd/conv.py`` (``BetaVAE_H``); ``capture`` turns the whole iteration into one HIP graph.
+``cl_ica_amd/conv.py`` (``BetaVAE_H``); ``capture`` turns the whole iteration into one HIP graph, ``capture_stream`` the iteration
+together with the draw of its batch (``dataset.StreamPairSampler``); ``train()`` on such a sampler with ``args.graph`` replays that graph.
 
 Data parallel (BASELINE.json configs[4]: "DDP over 4 x MI355X"; the reference itself has none): with an initialised
 ``torch.distributed`` group of world > 1 every rank encodes its own batch, the negatives pool is the autograd-aware
@@ -26,6 +27,7 @@ import torch.distributed as dist
 from .. import losses
 from ..distributed import gather_negatives
 from ..optim import Adam
+from .dataset import StreamPairSampler
 from .model import BetaVAE_H
 
 __all__ = ["Solver"]
@@ -80,6 +82,7 @@ class Solver(object):
         for src, dst in self._FIELDS.items():
             setattr(self, dst, getattr(args, src))
         self.data_loader = data_loader
+        self.graph = bool(getattr(args, "graph", False))          # train() on a StreamPairSampler: one graph replay per iteration
         self.global_iter = 0
         self.device = torch.device("cuda", torch.cuda.current_device())
         self.world = dist.get_world_size() if dist.is_initialized() else 1
@@ -129,6 +132,49 @@ class Solver(object):
             loss = self.train_iteration(x)
         return graph.replay, loss
 
+    def capture_stream(self, sampler, warmup: int = 3):
+        """``capture`` with the data inside: ONE HIP graph holding ``sampler.draw_into(x)`` (the next batch of the training stream, drawn
+        and gathered by one launch) followed by ``train_iteration(x)``.  Returns ``(replay, loss)``: ``replay()`` draws the next batch,
+        trains on it and refreshes the 0-dim tensor ``loss``; it also tells the sampler (``replayed()``), which refills the permutation
+        at epoch boundaries.  The `warmup` iterations run on the capture stream first, each on a fresh batch of the stream, as real
+        optimizer steps."""
+        replay, loss = self._capture_stream(sampler, warmup)
+        return replay, loss
+
+    def _capture_stream(self, sampler, warmup, on_step=None, acc=None):
+        """``capture_stream`` for the loop: ``on_step(loss)`` after every warm-up iteration (when it returns True the warm-up stops and
+        nothing is captured: ``(None, None)``); `acc`: a device fp32 scalar the graph adds every replay's loss to."""
+        if self.world > 1:
+            raise RuntimeError("Solver.capture_stream: the data-parallel step (gloo / RCCL collectives issued from Python) is not captured")
+        x = torch.empty(sampler.image_shape, dtype=torch.float32, device=self.device)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        stopped = False
+        with torch.cuda.stream(side):
+            for _ in range(max(1, warmup)):
+                sampler.draw_into(x)
+                total = self.train_iteration(x)
+                if on_step is not None and on_step(total.detach()):
+                    stopped = True
+                    break
+            sampler.prepare()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize(self.device)
+        if stopped:
+            return None, None
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            sampler.draw_into(x)
+            loss = self.train_iteration(x)
+            if acc is not None:
+                acc.add_(loss.detach())
+
+        def replay():
+            graph.replay()
+            sampler.replayed()
+
+        return replay, loss
+
     # ------------------------------------------------------------------ the loop
     def _batches(self):
         """Endless stream of image batches: the loader is re-iterated epoch after epoch, labels dropped."""
@@ -143,6 +189,8 @@ class Solver(object):
     def train(self):
         """Runs until ``max_iter`` iterations have been done; returns False (the reference's `failure` flag, never set there)."""
         self.net_mode(train=True)
+        if isinstance(self.data_loader, StreamPairSampler) and self.world == 1:
+            return self._train_stream(self.data_loader)
         window = _WindowMean(self.log_step)
         # data parallel: rank 0 alone owns log.csv and the checkpoints (replicas are identical after every step); the logged
         # value is the mean over the ranks' row blocks = the loss of the global batch
@@ -167,6 +215,49 @@ class Solver(object):
                         self.save_checkpoint(str(self.global_iter))
                 if self.global_iter >= self.max_iter:
                     break
+        return False
+
+    def _train_stream(self, sampler):
+        """The loop on a ``StreamPairSampler``: every batch comes from the sampler's one launch, the loss is summed in a device fp32
+        scalar and read at ``log_step`` boundaries only.  ``self.graph``: after the warm-up iterations (real iterations of the run, on
+        the capture stream) every iteration is one replay of the ``capture_stream`` graph; otherwise the same launches are issued
+        eagerly.  Both ways sum the loss in the same scalar in the same order, so they write the same ``log.csv``."""
+        acc = torch.zeros((), dtype=torch.float32, device=self.device)
+        pending = 0
+        with open(os.path.join(self.output_dir, "log.csv"), "a", 1) as log:
+            log.write("Total Loss\n")
+
+            def tick():
+                """Bookkeeping of one finished iteration whose loss sits in `acc`; True when the run is over."""
+                nonlocal pending
+                self.global_iter += 1
+                pending += 1
+                if pending == self.log_step:
+                    log.write("%.6f\n" % (acc.item() / self.log_step))
+                    acc.zero_()
+                    pending = 0
+                if self.global_iter % self.save_step == 0:
+                    self.save_checkpoint("last")
+                if self.global_iter % _MILESTONE == 0:
+                    self.save_checkpoint(str(self.global_iter))
+                return self.global_iter >= self.max_iter
+
+            def warm(total):
+                acc.add_(total)
+                return tick()
+
+            if self.graph:
+                replay, _ = self._capture_stream(sampler, 3, on_step=warm, acc=acc)
+                while replay is not None:
+                    replay()
+                    if tick():
+                        break
+            else:
+                x = torch.empty(sampler.image_shape, dtype=torch.float32, device=self.device)
+                while True:
+                    sampler.draw_into(x)
+                    if warm(self.train_iteration(x).detach()):
+                        break
         return False
 
     # ------------------------------------------------------------------ checkpoints (solver.py:98-128 layout)

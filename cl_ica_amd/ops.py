@@ -1451,6 +1451,69 @@ def kitti_gather_pairs(frames: torch.Tensor, first: torch.Tensor, second: torch.
     return images, labels
 
 
+def kitti_gather_frames(frames: torch.Tensor, frame_ids: torch.Tensor, latents: Optional[torch.Tensor] = None):
+    """float32 images [n, 1, H, W] (and labels [n, n_lat]) of the single frames `frame_ids` of a uint8 frame table [F, H, W] in HBM
+    (clica_kitti_gather_frames).  Ids handed over on the host are checked against the table here; ids that already live on the device
+    are not (that would be a host sync): the kernel clamps them, so an id outside the table gives its nearest frame."""
+    if not frames.is_cuda:
+        raise ClicaError(f"frames must live on the GPU (got device {frames.device}); cl_ica_amd runs only through its HIP kernels")
+    if frames.dtype != torch.uint8 or not frames.is_contiguous():
+        raise ValueError("frames must be a contiguous uint8 tensor [F, ...]")
+    F = frames.shape[0]
+    ids = torch.as_tensor(frame_ids)
+    if not ids.is_cuda and ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= F):
+        raise ValueError(f"frame_ids must lie in 0 .. {F - 1} (got {int(ids.min())} .. {int(ids.max())})")
+    ids = ids.to(device=frames.device, dtype=torch.int64).contiguous()
+    n = ids.numel()
+    if n == 0 or ids.dim() != 1:
+        raise ValueError(f"frame_ids must be a non-empty 1-D list (got shape {tuple(ids.shape)})")
+    images = torch.empty((n, 1) + tuple(frames.shape[1:]), dtype=torch.float32, device=frames.device)
+    labels = lat = None
+    n_lat = 0
+    if latents is not None:
+        require_cuda(latents, "latents")
+        lat = latents.detach().to(torch.float32).contiguous()
+        n_lat = lat.shape[1]
+        labels = torch.empty((n, n_lat), dtype=torch.float32, device=frames.device)
+    check(load().clica_kitti_gather_frames(frames.data_ptr(), frames[0].numel(), F, ids.data_ptr(), n, images.data_ptr(), ptr(lat), n_lat,
+                                           ptr(labels), stream_ptr()), "clica_kitti_gather_frames")
+    return images, labels
+
+
+def kitti_sample_pairs(frames: torch.Tensor, latents: Optional[torch.Tensor], cumlens: torch.Tensor, seq_start: torch.Tensor,
+                       seq_len: torch.Tensor, order: torch.Tensor, n_pairs: int, max_delta_t: int, seed: int, state: torch.Tensor,
+                       images: torch.Tensor, labels: Optional[torch.Tensor] = None, drawn: Optional[torch.Tensor] = None) -> None:
+    """The next batch of the KITTI-masks training stream, drawn and gathered by one launch into `images` [2 B, 1, H, W] (and `labels`
+    [2 B, n_lat]); `state` (int64 [2]: batch counter, ticket) is advanced by the launch itself (clica_kitti_sample_pairs, include/clica.h).
+    `drawn`: optional int64 [4, B] that receives (index, t, first frame, second frame) per pair.  No tensor is allocated or converted
+    here: every argument is a device buffer the caller owns, so the call is capture-safe."""
+    for name, t, dt in (("frames", frames, torch.uint8), ("cumlens", cumlens, torch.int64), ("seq_start", seq_start, torch.int64),
+                        ("seq_len", seq_len, torch.int64), ("order", order, torch.int64), ("state", state, torch.int64),
+                        ("images", images, torch.float32), ("labels", labels, torch.float32), ("latents", latents, torch.float32),
+                        ("drawn", drawn, torch.int64)):
+        if t is None and name in ("labels", "latents", "drawn"):
+            continue
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise ClicaError(f"{name} must live on the GPU; cl_ica_amd runs only through its HIP kernels")
+        if t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} tensor (got {t.dtype}, contiguous={t.is_contiguous()})")
+    B, elems, n_seq, n_items = int(n_pairs), frames[0].numel(), cumlens.numel(), order.numel()
+    n_lat = latents.shape[1] if latents is not None else 0
+    if seq_start.numel() != n_seq or seq_len.numel() != n_seq or state.numel() < 2:
+        raise ValueError("cumlens / seq_start / seq_len must have one entry per sequence and state two words")
+    if B >= 1 and images.numel() != 2 * B * elems:
+        raise ValueError(f"images holds {images.numel()} values for {B} pairs of {elems} pixels")
+    if labels is not None and (latents is None or labels.numel() != 2 * B * n_lat):
+        raise ValueError(f"labels must hold 2 x {B} x {n_lat} values and needs a latent table")
+    if drawn is not None and tuple(drawn.shape) != (4, max(B, 0)):
+        raise ValueError(f"drawn must be int64 [4, {B}]")
+    outs = [drawn[k].data_ptr() for k in range(4)] if drawn is not None else [None] * 4
+    check(load().clica_kitti_sample_pairs(frames.data_ptr(), elems, frames.shape[0], ptr(latents), n_lat, cumlens.data_ptr(),
+                                          seq_start.data_ptr(), seq_len.data_ptr(), n_seq, n_items, order.data_ptr(), B, int(max_delta_t),
+                                          int(seed) & (2 ** 64 - 1), state.data_ptr(), images.data_ptr(), ptr(labels), *outs, stream_ptr()),
+          "clica_kitti_sample_pairs")
+
+
 def _image_table(table: torch.Tensor) -> Tuple[int, int, int, int]:
     if not torch.is_tensor(table):
         raise ValueError("table must be a uint8 tensor [N, H, W, C]")

@@ -953,6 +953,26 @@ int clica_nn_search(const float* table, int64_t ldt, int64_t n_table, const floa
 int clica_kitti_gather_pairs(const uint8_t* frames, int64_t frame_elems, int64_t n_frames, const int64_t* first_frame,
                              const int64_t* second_frame, int64_t n_pairs, float* images, const float* latents, int32_t n_latents,
                              float* labels, clica_stream_t stream);
+/* Single frames: images[j] = float(frames[frame_ids[j]]) ([n][frame_elems]), labels[j] = latents[frame_ids[j]] (optional). */
+int clica_kitti_gather_frames(const uint8_t* frames, int64_t frame_elems, int64_t n_frames, const int64_t* frame_ids, int64_t n,
+                              float* images, const float* latents, int32_t n_latents, float* labels, clica_stream_t stream);
+/* The NEXT batch of the training stream, drawn and gathered by one launch (DataLoader(shuffle=True, drop_last=True) + __getitem__ +
+ * custom_collate).  All tables are device memory: cumlens / seq_start / seq_len int64 [n_seq] (cumulative count of start items, first
+ * frame and frame count per sequence), n_items = cumlens[n_seq - 1], order int64 [n_items] = the current epoch's permutation (refilled
+ * by the caller between epochs, at the same address), state = two 64-bit words owned by the caller, zero at the start: [0] the batch
+ * counter c, [1] a ticket word.  With steps_per_epoch = n_items / n_pairs, pair i takes
+ *   index = order[(c mod steps_per_epoch) n_pairs + i],  t = 1 + mulhi32(philox4x32-10(seed; i, c, stream "KITT"), max_delta_t),
+ *   seq = #{cumlens <= index},  start = index - cumlens[seq - 1] (0 for seq = 0),  end = min(start + t, seq_len[seq] - 1),
+ * and writes frames seq_start[seq] + start / + end as images[2 i] / images[2 i + 1] (and their latents as labels).  The launch itself
+ * advances state[0] by one (the last workgroup to finish, found by the ticket), so replays of a captured launch walk the stream.
+ * out_index / out_t / out_first / out_second: optional int64 [n_pairs], what was drawn.
+ * CLICA_E_INVALID (no launch): NULL pointer, frame_elems % 4, misaligned frames (4) / images (16) / state (8), max_delta_t < 1,
+ * n_pairs < 1, n_pairs > n_items, labels without latents or with more than 128 columns. */
+int clica_kitti_sample_pairs(const uint8_t* frames, int64_t frame_elems, int64_t n_frames, const float* latents, int32_t n_latents,
+                             const int64_t* cumlens, const int64_t* seq_start, const int64_t* seq_len, int64_t n_seq, int64_t n_items,
+                             const int64_t* order, int64_t n_pairs, int32_t max_delta_t, uint64_t seed, uint64_t* state, float* images,
+                             float* labels, int64_t* out_index, int64_t* out_t, int64_t* out_first, int64_t* out_second,
+                             clica_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Image batches from a uint8 table in HBM  --  the image half of ThreeDIdentDataset / SequentialThreeDIdentDataset
