@@ -935,7 +935,9 @@ int clica_mixing_fwd_act(const float* Z, int64_t ldz, const float* W, int32_t n_
  * Exact k-nearest-neighbour search in squared L2 over a latent table in HBM  --  the lookup
  * datasets/threedident_dataset.py:71, 83, 104-105 does on the host with faiss.IndexFlatL2 (`index.add(latents)`,
  * `index.search(z, 1)`, `index.search(z_tilde, 2)`): dist[i, c] = |query_i - table_idx[i, c]|^2 ascending in c, ties to the
- * lower row; idx is int64 like faiss' labels (-1 where the table has fewer than k rows); dist may be NULL.
+ * lower row; idx is int64 like faiss' labels (-1 where the table has fewer than k rows, at dist = +inf); dist may be NULL.
+ * A table row with a NaN coordinate is never returned.  A row at infinite distance (an infinite coordinate) ranks behind every
+ * finite one: it is returned only when fewer than k rows at finite distance exist, and such a column may hold -1 instead.
  * 1 <= n <= 64, 1 <= k <= 4.
  * ---------------------------------------------------------------------------------- */
 int clica_nn_search_workspace_bytes(int64_t n_query, int64_t n_table, int32_t n, int32_t k, size_t* bytes);
@@ -963,7 +965,9 @@ int clica_kitti_gather_frames(const uint8_t* frames, int64_t frame_elems, int64_
  * counter c, [1] a ticket word.  With steps_per_epoch = n_items / n_pairs, pair i takes
  *   index = order[(c mod steps_per_epoch) n_pairs + i],  t = 1 + mulhi32(philox4x32-10(seed; i, c, stream "KITT"), max_delta_t),
  *   seq = #{cumlens <= index},  start = index - cumlens[seq - 1] (0 for seq = 0),  end = min(start + t, seq_len[seq] - 1),
- * and writes frames seq_start[seq] + start / + end as images[2 i] / images[2 i + 1] (and their latents as labels).  The launch itself
+ * and writes frames seq_start[seq] + start / + end as images[2 i] / images[2 i + 1] (and their latents as labels).  The draw of t is
+ * part of what makes a run reproducible: the Philox counter is the four 32-bit words (i, c >> 32, c & 0xffffffff, 0x4B495454 "KITT"),
+ * the key (seed & 0xffffffff, seed >> 32), and t = 1 + ((output word 0 * max_delta_t) >> 32) in 64-bit arithmetic.  The launch itself
  * advances state[0] by one (the last workgroup to finish, found by the ticket), so replays of a captured launch walk the stream.
  * out_index / out_t / out_first / out_second: optional int64 [n_pairs], what was drawn.
  * CLICA_E_INVALID (no launch): NULL pointer, frame_elems % 4, misaligned frames (4) / images (16) / state (8), max_delta_t < 1,
