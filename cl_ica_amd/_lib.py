@@ -295,6 +295,13 @@ SIGNATURES: Dict[str, list] = {
                                            c_i64, C.c_void_p, C.c_void_p],
 }
 
+# the channels-last units and pools on bf16 activations: the argument lists of their fp32 twins (every pointer travels as void*)
+BF16_TWINS = ("clica_bn2d_nhwc_act_fwd_train", "clica_bn2d_nhwc_act_fwd_eval", "clica_bn2d_nhwc_act_bwd",
+              "clica_bn2d_nhwc_act_maxpool_fwd_train", "clica_bn2d_nhwc_act_maxpool_fwd_eval", "clica_bn2d_nhwc_act_maxpool_bwd",
+              "clica_avgpool2d_global_nhwc_fwd", "clica_avgpool2d_global_nhwc_bwd")
+for _name in BF16_TWINS:
+    SIGNATURES[_name + "_bf16"] = list(SIGNATURES[_name])
+
 _lib: Optional[C.CDLL] = None
 
 

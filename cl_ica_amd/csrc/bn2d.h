@@ -259,6 +259,43 @@ __device__ __forceinline__ void store(float* __restrict__ p, const float* v) {
   }
 }
 
+// bf16 activations, carried as their 16 bits.  bf16 -> fp32 is the shift (exact); fp32 -> bf16 rounds to nearest, ties to even, as
+// Tensor.to(torch.bfloat16) does (a NaN becomes the quiet NaN 0x7fc0 with the sign dropped, c10's rule).  Every kernel computes in fp32
+// on the widened values, so a bf16 instance has the bits of the fp32 one on the upcast input, rounded once at the store.
+using bf16_t = uint16_t;
+__device__ __forceinline__ float to_f32(float v) { return v; }
+__device__ __forceinline__ float to_f32(bf16_t v) { return __uint_as_float((uint32_t)v << 16); }
+__device__ __forceinline__ bf16_t bf16_rne(float f) {
+  const uint32_t u = __float_as_uint(f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (bf16_t)0x7fc0u;
+  return (bf16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+__device__ __forceinline__ void from_f32(float* p, float v) { *p = v; }
+__device__ __forceinline__ void from_f32(bf16_t* p, float v) { *p = bf16_rne(v); }
+
+// the same lanes and values on bf16: AL is one 8-byte access (the pointer is 8-byte aligned), else scalar 2-byte accesses
+template <int VEC, bool AL>
+__device__ __forceinline__ void load(const bf16_t* __restrict__ p, float* v) {
+  if (VEC == 4 && AL) {
+    const uint2 t = *reinterpret_cast<const uint2*>(p);
+    v[0] = __uint_as_float(t.x << 16); v[1] = __uint_as_float(t.x & 0xffff0000u);
+    v[2] = __uint_as_float(t.y << 16); v[3] = __uint_as_float(t.y & 0xffff0000u);
+  } else {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) v[k] = to_f32(p[k]);
+  }
+}
+template <int VEC, bool AL>
+__device__ __forceinline__ void store(bf16_t* __restrict__ p, const float* v) {
+  if (VEC == 4 && AL) {
+    *reinterpret_cast<uint2*>(p) = make_uint2((uint32_t)bf16_rne(v[0]) | (uint32_t)bf16_rne(v[1]) << 16,
+                                              (uint32_t)bf16_rne(v[2]) | (uint32_t)bf16_rne(v[3]) << 16);
+  } else {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) p[k] = bf16_rne(v[k]);
+  }
+}
+
 // the lanes of a wave, then the waves of the workgroup in wave order: thread 0 ends with the workgroup's sums
 __device__ __forceinline__ void block_sum2(float& a, float& b, float* sh /*[kWaves * 2]*/) {
 #pragma unroll

@@ -1,5 +1,8 @@
 // The BatchNorm2d unit of bn2d.hip -- z = gamma xhat + beta (+ r), y = lrelu(z, slope), and its backward from the saved output -- and the
 // global average pool on DENSE CHANNELS-LAST fp32 activations: an NHWC tensor is the row-major matrix x[M = N H W, C], row = pixel.
+// Every kernel takes the activations' element type T: float, or bf16 as its 16 bits (bn2d.h: widened exactly on load, rounded to nearest
+// even on store).  Statistics, parameters, partials, LDS and every accumulation are fp32 in both, and the geometry does not know T: a
+// bf16 instance computes what the fp32 one computes on the upcast input.
 //
 // Geometry "rows" (bn2d.h, rows_geometry): a lane owns VEC consecutive channels (4 when C % 4 == 0, else 1) and walks down the rows; lpr
 // lanes cover a row (or a 64-lane chunk of it: grid.x), a wave 64 / lpr consecutive rows, the workgroup rps = 256 / lpr rows per step.
@@ -13,7 +16,7 @@
 // Backward: rows_sums_k and rows_bwd_apply_k, the same pair.  Inference: rows_apply_k<.., false>, one launch.
 // The reduction tree of a channel: per lane over its rows m0 + row, m0 + row + rps, ... (blocks of four rows two-pass in registers, as
 // bn2d.hip), the lanes of a wave that hold the channel by shuffles (lane l takes lane l + off, off = 32 .. lpr), the waves through LDS
-// in wave order, the splits as above.  It depends on (M, C) alone; AL only picks 16-byte accesses.
+// in wave order, the splits as above.  It depends on (M, C) alone; AL only picks one access per lane (16 bytes of fp32, 8 of bf16).
 // The stem unit with its max-pool, P = maxpool 3 x 3 / 2 / 1 of y, on the same lanes (bn2d.h, PoolRows): rows_stats_k, then
 // pool_rows_fwd_k, which merges and finishes as rows_apply_k and writes each output pixel's first maximum; inference: one launch;
 // backward: pool_rows_sums_k (a slot per window: the sums need no pixels) and pool_rows_bwd_apply_k, which recomputes y per tile of
@@ -41,8 +44,8 @@ struct Lane {
 };
 
 // ------------------------------------------------------------------------------------------------ statistics: grid (chunks, S)
-template <int VEC, bool AL>
-__global__ __launch_bounds__(kThreads) void rows_stats_k(const float* __restrict__ x, int64_t M, int C, int lpr, int64_t per,
+template <class T, int VEC, bool AL>
+__global__ __launch_bounds__(kThreads) void rows_stats_k(const T* __restrict__ x, int64_t M, int C, int lpr, int64_t per,
                                                         float* __restrict__ part) {
   __shared__ float sh[VEC * bn::kColumnStatLds];
   const Lane<VEC> ln(C, lpr);
@@ -55,7 +58,7 @@ __global__ __launch_bounds__(kThreads) void rows_stats_k(const float* __restrict
   if (ln.in) {
     float pivot[VEC];                                      // moments of x - x[0, c]
     load<VEC, AL>(x + ln.c0, pivot);
-    const float* xp = x + ln.c0;
+    const T* xp = x + ln.c0;
     const int64_t step = ln.rps;
     int64_t m = m0 + ln.row;
     for (; m + 3 * step < m1; m += 4 * step) {             // four rows' loads in flight, then one block of 4 values per channel
@@ -145,11 +148,11 @@ __device__ __forceinline__ void merged_sums(const Merger& mr, const float* __res
 
 // ------------------------------------------------------------------------------------------------ apply: grid (chunks, T)
 // TRAIN: batch statistics from the partials, tile 0 holds the writers; otherwise the running statistics (inference, no LDS, no barrier).
-template <int VEC, bool AL, bool TRAIN>
-__global__ __launch_bounds__(kThreads) void rows_apply_k(const float* __restrict__ x, const float* __restrict__ r, const float* __restrict__ gamma,
+template <class T, int VEC, bool AL, bool TRAIN>
+__global__ __launch_bounds__(kThreads) void rows_apply_k(const T* __restrict__ x, const T* __restrict__ r, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, int64_t M, int C, int lpr, int mg, int ms, int S,
                                                         int64_t tile, float Mf, float eps, float momentum, float slope,
-                                                        const float* __restrict__ part, float* __restrict__ y, float* __restrict__ save_mean,
+                                                        const float* __restrict__ part, T* __restrict__ y, float* __restrict__ save_mean,
                                                         float* __restrict__ save_invstd, float* running_mean, float* running_var) {
   __shared__ float sh[TRAIN ? kMergeLds : 1];
   __shared__ float shn[TRAIN ? 2 * kThreads : 1];          // mean, invstd of the chunk's channels
@@ -159,7 +162,7 @@ __global__ __launch_bounds__(kThreads) void rows_apply_k(const float* __restrict
     const Merger mr(C, lpr, VEC);
     const Stat t = merged_stat(mr, part, S, C, mg, ms, sh);
     if (mr.first()) {
-      const bn::Norm n = bn::finish_train(t, x[mr.c], Mf, eps, momentum, mr.c, blockIdx.y == 0, save_mean, save_invstd, running_mean,
+      const bn::Norm n = bn::finish_train(t, to_f32(x[mr.c]), Mf, eps, momentum, mr.c, blockIdx.y == 0, save_mean, save_invstd, running_mean,
                                           running_var);
       shn[mr.ci] = n.mean; shn[kThreads + mr.ci] = n.invstd;
     }
@@ -193,8 +196,8 @@ __global__ __launch_bounds__(kThreads) void rows_apply_k(const float* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------ backward sums: grid (chunks, S)
-template <int VEC, bool AL>
-__global__ __launch_bounds__(kThreads) void rows_sums_k(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ dy,
+template <class T, int VEC, bool AL>
+__global__ __launch_bounds__(kThreads) void rows_sums_k(const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ dy,
                                                        const float* __restrict__ save_mean, const float* __restrict__ save_invstd, int64_t M,
                                                        int C, int lpr, int64_t per, float slope, float* __restrict__ part) {
   __shared__ float sh[VEC * bn::kColumnSumsLds];
@@ -233,12 +236,12 @@ __global__ __launch_bounds__(kThreads) void rows_sums_k(const float* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------ backward apply: grid (chunks, T)
-template <int VEC, bool AL>
-__global__ __launch_bounds__(kThreads) void rows_bwd_apply_k(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ dy,
+template <class T, int VEC, bool AL>
+__global__ __launch_bounds__(kThreads) void rows_bwd_apply_k(const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ dy,
                                                             const float* __restrict__ gamma, const float* __restrict__ save_mean,
                                                             const float* __restrict__ save_invstd, int64_t M, int C, int lpr, int mg, int ms,
                                                             int S, int64_t tile, float Mf, float slope, const float* __restrict__ part,
-                                                            float* __restrict__ dx, float* __restrict__ dr, float* __restrict__ dgamma,
+                                                            T* __restrict__ dx, T* __restrict__ dr, float* __restrict__ dgamma,
                                                             float* __restrict__ dbeta) {
   __shared__ float sh[kMergeLds];
   __shared__ float shs[2 * kThreads];                      // sum dz, sum dz xhat of the chunk's channels
@@ -288,7 +291,10 @@ struct Tag {
   static constexpr bool AL = AL_;
 };
 
-// f(Tag<VEC, AL>): C alone picks VEC (the reduction order); `al` only picks 16-byte accesses
+// f(Tag<VEC, AL>): C alone picks VEC (the reduction order); `al` only picks one access per lane: 16 bytes of fp32, 8 bytes of bf16
+template <class T>
+static inline bool lane_aligned(const T* p) { return (reinterpret_cast<uintptr_t>(p) & (4 * sizeof(T) - 1)) == 0; }
+
 template <class F>
 static void with_lane(int vec, bool al, F&& f) {
   if (vec == 4) {
@@ -299,41 +305,43 @@ static void with_lane(int vec, bool al, F&& f) {
   }
 }
 
-template <bool TRAIN>
-static void launch_apply(hipStream_t st, const float* x, const float* r, const float* gamma, const float* beta, int64_t M, int C, float eps,
-                         float momentum, float slope, const float* part, float* y, float* save_mean, float* save_invstd, float* rm,
+template <bool TRAIN, class T>
+static void launch_apply(hipStream_t st, const T* x, const T* r, const float* gamma, const float* beta, int64_t M, int C, float eps,
+                         float momentum, float slope, const float* part, T* y, float* save_mean, float* save_invstd, float* rm,
                          float* rv) {
   const Rows geo = rows_geometry(M, C);
   const dim3 grid((unsigned)geo.chunks, (unsigned)geo.T), block(kThreads);
-  const bool al = aligned16(x) && aligned16(y) && (!r || aligned16(r));
+  const bool al = lane_aligned(x) && lane_aligned(y) && (!r || lane_aligned(r));
   with_lane(geo.vec, al, [&](auto tag) {
-    using T = decltype(tag);
-    hipLaunchKernelGGL((rows_apply_k<T::VEC, T::AL, TRAIN>), grid, block, 0, st, x, r, gamma, beta, M, C, geo.lpr, geo.mg, geo.ms, geo.S,
+    using L = decltype(tag);
+    hipLaunchKernelGGL((rows_apply_k<T, L::VEC, L::AL, TRAIN>), grid, block, 0, st, x, r, gamma, beta, M, C, geo.lpr, geo.mg, geo.ms, geo.S,
                        geo.tile, (float)M, eps, momentum, slope, part, y, save_mean, save_invstd, rm, rv);
   });
 }
 
 // ------------------------------------------------------------------------------------------------ global average pool, x[N, HW, C]
 // thread = (n, c), lanes along C: the HW values of a channel in pixel order
-__global__ __launch_bounds__(kThreads) void avgpool_fwd_k(const float* __restrict__ x, int64_t NC, int HW, int C, float inv,
+template <class T>
+__global__ __launch_bounds__(kThreads) void avgpool_fwd_k(const T* __restrict__ x, int64_t NC, int HW, int C, float inv,
                                                          float* __restrict__ y) {
   const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (t >= NC) return;
   const int64_t n = t / C;
-  const float* p = x + n * HW * C + (t - n * C);
+  const T* p = x + n * HW * C + (t - n * C);
   float s = 0.f;
 #pragma unroll 4
-  for (int k = 0; k < HW; ++k) s += p[(int64_t)k * C];
+  for (int k = 0; k < HW; ++k) s += to_f32(p[(int64_t)k * C]);
   y[t] = s * inv;
 }
 
 // thread = element (n, k, c)
+template <class T>
 __global__ __launch_bounds__(kThreads) void avgpool_bwd_k(const float* __restrict__ dy, int64_t total, int HW, int C, float inv,
-                                                         float* __restrict__ dx) {
+                                                         T* __restrict__ dx) {
   const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (t >= total) return;
   const int64_t nk = t / C;
-  dx[t] = dy[(nk / HW) * C + (t - nk * C)] * inv;
+  from_f32(dx + t, dy[(nk / HW) * C + (t - nk * C)] * inv);
 }
 
 // ------------------------------------------------------------------------------------------------ the stem unit with its max-pool
@@ -343,8 +351,8 @@ __global__ __launch_bounds__(kThreads) void avgpool_bwd_k(const float* __restric
 // (rows, then columns), its maximum and the position 0 .. 8 of the maximum's first occurrence -- strict >, torch's rule and window_max's
 // of pool2d.hip, so the bits of that first maximum, signed zeros included -- and xhat of that pixel in xm.  The nine loads are issued
 // before the first comparison; a position outside the plane loads the window's centre, which is always inside, and never wins.
-template <int VEC, bool AL>
-__device__ __forceinline__ void window_first_max(const float* __restrict__ xn, int ho, int wo, int H, int W, int C, const bn::Norm* nm,
+template <int VEC, bool AL, class T>
+__device__ __forceinline__ void window_first_max(const T* __restrict__ xn, int ho, int wo, int H, int W, int C, const bn::Norm* nm,
                                                  const float* g, const float* b, float slope, float* m, int* code, float* xm) {
   float v[9][VEC];
   bool ok[9];
@@ -374,11 +382,11 @@ __device__ __forceinline__ void window_first_max(const float* __restrict__ xn, i
 }
 
 // forward: grid (chunks, Tf); a slot (Lane::row) owns an output pixel o = (n, ho, wo) of its run of `tile`.  TRAIN as rows_apply_k.
-template <int VEC, bool AL, bool TRAIN>
-__global__ __launch_bounds__(kThreads) void pool_rows_fwd_k(const float* __restrict__ x, const float* __restrict__ gamma,
+template <class T, int VEC, bool AL, bool TRAIN>
+__global__ __launch_bounds__(kThreads) void pool_rows_fwd_k(const T* __restrict__ x, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, int64_t Mo, int C, int H, int W, int Ho, int Wo,
                                                            int lpr, int mg, int ms, int S, int64_t tile, float Mf, float eps, float momentum,
-                                                           float slope, const float* __restrict__ part, float* __restrict__ P,
+                                                           float slope, const float* __restrict__ part, T* __restrict__ P,
                                                            float* __restrict__ save_mean, float* __restrict__ save_invstd,
                                                            float* running_mean, float* running_var) {
   __shared__ float sh[TRAIN ? kMergeLds : 1];
@@ -389,7 +397,7 @@ __global__ __launch_bounds__(kThreads) void pool_rows_fwd_k(const float* __restr
     const Merger mr(C, lpr, VEC);
     const Stat t = merged_stat(mr, part, S, C, mg, ms, sh);
     if (mr.first()) {
-      const bn::Norm n = bn::finish_train(t, x[mr.c], Mf, eps, momentum, mr.c, blockIdx.y == 0, save_mean, save_invstd, running_mean,
+      const bn::Norm n = bn::finish_train(t, to_f32(x[mr.c]), Mf, eps, momentum, mr.c, blockIdx.y == 0, save_mean, save_invstd, running_mean,
                                           running_var);
       shn[mr.ci] = n.mean; shn[kThreads + mr.ci] = n.invstd;
     }
@@ -422,8 +430,8 @@ __global__ __launch_bounds__(kThreads) void pool_rows_fwd_k(const float* __restr
 //   sum over pixels of dz = sum over windows of d,      sum over pixels of dz xhat = sum over windows of d xhat(first maximum):
 // the sums need the windows, not the pixels -- no LDS staging, no halo.  The partial's tree: per lane over its windows in order, then
 // lanes and waves as rows_sums_k.
-template <int VEC, bool AL>
-__global__ __launch_bounds__(kThreads) void pool_rows_sums_k(const float* __restrict__ x, const float* __restrict__ dP,
+template <class T, int VEC, bool AL>
+__global__ __launch_bounds__(kThreads) void pool_rows_sums_k(const T* __restrict__ x, const T* __restrict__ dP,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
                                                             const float* __restrict__ save_mean, const float* __restrict__ save_invstd,
                                                             int64_t Mo, int C, int H, int W, int Ho, int Wo, int lpr, int64_t per,
@@ -535,13 +543,13 @@ __device__ __forceinline__ void pool_rows_dz(const float* sd, const unsigned cha
 // windows i = row, row + rps, ... of the tile's staged (BH + 1) x (BW + 1) (the part inside the output plane) and leaves dP gate(y_max)
 // in sd and the position of the first maximum in sc, entry (window, channel of the chunk); after a barrier it takes pixels i = row,
 // row + rps, ... of the tile's own (row-major), gathers dz and writes dx.  Lanes without channels only keep the barriers company.
-template <int VEC, bool AL>
-__global__ __launch_bounds__(kThreads) void pool_rows_bwd_apply_k(const float* __restrict__ x, const float* __restrict__ dP,
+template <class T, int VEC, bool AL>
+__global__ __launch_bounds__(kThreads) void pool_rows_bwd_apply_k(const T* __restrict__ x, const T* __restrict__ dP,
                                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                  const float* __restrict__ save_mean, const float* __restrict__ save_invstd,
                                                                  PoolPlane g, int lpr, int mg, int ms, int S, int64_t tiles, int64_t per,
                                                                  float Mf, float slope, const float* __restrict__ part,
-                                                                 float* __restrict__ dx, float* __restrict__ dgamma,
+                                                                 T* __restrict__ dx, float* __restrict__ dgamma,
                                                                  float* __restrict__ dbeta) {
   __shared__ float sh[kMergeLds];
   __shared__ float shs[2 * kThreads];                      // sum dz, sum dz xhat of the chunk's channels
@@ -583,8 +591,8 @@ __global__ __launch_bounds__(kThreads) void pool_rows_bwd_apply_k(const float* _
     const int wh = nh + 1 < g.Ho - ho0 ? nh + 1 : g.Ho - ho0, ww = nw + 1 < g.Wo - wo0 ? nw + 1 : g.Wo - wo0;      // staged
     const int ph = 2 * nh < g.H - 2 * ho0 ? 2 * nh : g.H - 2 * ho0, pw = 2 * nw < g.W - 2 * wo0 ? 2 * nw : g.W - 2 * wo0;      // own pixels
     if (ln.in) {
-      const float* xn = x + n * g.H * g.W * g.C + ln.c0;
-      const float* dpn = dP + n * g.Ho * g.Wo * g.C + ln.c0;
+      const T* xn = x + n * g.H * g.W * g.C + ln.c0;
+      const T* dpn = dP + n * g.Ho * g.Wo * g.C + ln.c0;
       for (int i = ln.row; i < wh * ww; i += ln.rps) {
         const int lh = i / ww, lw = i - lh * ww, ho = ho0 + lh, wo = wo0 + lw;
         float m[VEC], xm[VEC], d[VEC];
@@ -618,16 +626,16 @@ __global__ __launch_bounds__(kThreads) void pool_rows_bwd_apply_k(const float* _
   }
 }
 
-template <bool TRAIN>
-static void launch_pool_fwd(hipStream_t st, const float* x, const float* gamma, const float* beta, int64_t N, int C, int H, int W, float eps,
-                            float momentum, float slope, const float* part, float* P, float* save_mean, float* save_invstd, float* rm,
+template <bool TRAIN, class T>
+static void launch_pool_fwd(hipStream_t st, const T* x, const float* gamma, const float* beta, int64_t N, int C, int H, int W, float eps,
+                            float momentum, float slope, const float* part, T* P, float* save_mean, float* save_invstd, float* rm,
                             float* rv) {
   const PoolRows geo = pool_rows_geometry(N, C, H, W);
   const Rows& r = geo.rows;
   const dim3 grid((unsigned)r.chunks, (unsigned)geo.Tf), block(kThreads);
-  with_lane(r.vec, aligned16(x) && aligned16(P), [&](auto tag) {
-    using T = decltype(tag);
-    hipLaunchKernelGGL((pool_rows_fwd_k<T::VEC, T::AL, TRAIN>), grid, block, 0, st, x, gamma, beta, N * geo.Ho * geo.Wo, C, H, W, geo.Ho,
+  with_lane(r.vec, lane_aligned(x) && lane_aligned(P), [&](auto tag) {
+    using L = decltype(tag);
+    hipLaunchKernelGGL((pool_rows_fwd_k<T, L::VEC, L::AL, TRAIN>), grid, block, 0, st, x, gamma, beta, N * geo.Ho * geo.Wo, C, H, W, geo.Ho,
                        geo.Wo, r.lpr, r.mg, r.ms, r.S, geo.tile_f, (float)(N * H * W), eps, momentum, slope, part, P, save_mean, save_invstd,
                        rm, rv);
   });
@@ -639,13 +647,27 @@ static void launch_pool_fwd(hipStream_t st, const float* x, const float* gamma, 
 
 using namespace clica;
 using bn2d::nhwc::with_lane;
+using bn2d::nhwc::lane_aligned;
 
+// The entry points come in pairs, fp32 and bf16 activations, on one body each: `fn` is the entry point's name, T the activations'
+// element (float, or bf16 as its 16 bits).  Checks, geometry, workspace and return codes do not depend on T.
 #define CLICA_BN2D_NHWC_SHAPE(fn, min_M)                                                                                       \
   CLICA_CHECK_ARG(M >= (min_M) && C >= 1 && C <= bn2d::kMaxC && (double)M * (double)C < 1e18,                                  \
-                  fn ": M=%lld C=%d (M = N H W >= %d, 1 <= C <= %d)", (long long)M, C, (min_M), bn2d::kMaxC)
+                  "%s: M=%lld C=%d (M = N H W >= %d, 1 <= C <= %d)", fn, (long long)M, C, (min_M), bn2d::kMaxC)
 
 #define CLICA_BN2D_NHWC_SLOPE(fn) \
-  CLICA_CHECK_ARG(slope >= 0.f, fn ": slope=%g must be >= 0 (the backward recovers the gate from the output)", slope)
+  CLICA_CHECK_ARG(slope >= 0.f, "%s: slope=%g must be >= 0 (the backward recovers the gate from the output)", fn, slope)
+
+// CLICA_BN_WORKSPACE (bn_core.h) with the entry point's name at run time
+#define CLICA_BN2D_NHWC_WORKSPACE(fn, need, size_fn, short_code)                                                       \
+  do {                                                                                                                 \
+    CLICA_CHECK_ARG(bn2d::aligned16(workspace), "%s: workspace must be 16-byte aligned", fn);                          \
+    const size_t need_ = (need);                                                                                       \
+    if (workspace_bytes < need_) {                                                                                     \
+      ::clica::set_error("%s: workspace of %zu bytes, %zu needed (" size_fn ")", fn, workspace_bytes, need_);          \
+      return short_code;                                                                                               \
+    }                                                                                                                  \
+  } while (0)
 
 extern "C" int clica_bn2d_nhwc_workspace_bytes(int64_t M, int32_t C, size_t* bytes) {
   CLICA_CHECK_ARG(bytes != nullptr, "clica_bn2d_nhwc_workspace_bytes: bytes is NULL");
@@ -654,73 +676,121 @@ extern "C" int clica_bn2d_nhwc_workspace_bytes(int64_t M, int32_t C, size_t* byt
   return CLICA_OK;
 }
 
-extern "C" int clica_bn2d_nhwc_act_fwd_train(const float* X, const float* R, const float* gamma, const float* beta, int64_t M, int32_t C,
-                                             float eps, float momentum, float slope, float* Y, float* save_mean, float* save_invstd,
-                                             float* running_mean, float* running_var, void* workspace, size_t workspace_bytes,
-                                             clica_stream_t stream) {
-  CLICA_BN2D_NHWC_SHAPE("clica_bn2d_nhwc_act_fwd_train", 2);
-  CLICA_BN2D_NHWC_SLOPE("clica_bn2d_nhwc_act_fwd_train");
-  CLICA_CHECK_ARG(X && gamma && beta && Y && save_mean && save_invstd && workspace, "clica_bn2d_nhwc_act_fwd_train: NULL pointer");
-  CLICA_BN_WORKSPACE("clica_bn2d_nhwc_act_fwd_train", bn2d::rows_workspace_bytes(M, C), "clica_bn2d_nhwc_workspace_bytes", CLICA_E_INVALID);
+namespace {
+
+template <class T>
+int act_fwd_train(const char* fn, const T* X, const T* R, const float* gamma, const float* beta, int64_t M, int32_t C, float eps,
+                  float momentum, float slope, T* Y, float* save_mean, float* save_invstd, float* running_mean, float* running_var,
+                  void* workspace, size_t workspace_bytes, clica_stream_t stream) {
+  CLICA_BN2D_NHWC_SHAPE(fn, 2);
+  CLICA_BN2D_NHWC_SLOPE(fn);
+  CLICA_CHECK_ARG(X && gamma && beta && Y && save_mean && save_invstd && workspace, "%s: NULL pointer", fn);
+  CLICA_BN2D_NHWC_WORKSPACE(fn, bn2d::rows_workspace_bytes(M, C), "clica_bn2d_nhwc_workspace_bytes", CLICA_E_INVALID);
   hipStream_t st = as_stream(stream);
   float* part = static_cast<float*>(workspace);
   const bn2d::Rows geo = bn2d::rows_geometry(M, C);
   const dim3 grid((unsigned)geo.chunks, (unsigned)geo.S), block(bn2d::kThreads);
-  with_lane(geo.vec, bn2d::aligned16(X), [&](auto tag) {
-    using T = decltype(tag);
-    hipLaunchKernelGGL((bn2d::nhwc::rows_stats_k<T::VEC, T::AL>), grid, block, 0, st, X, M, (int)C, geo.lpr, geo.per, part);
+  with_lane(geo.vec, lane_aligned(X), [&](auto tag) {
+    using L = decltype(tag);
+    hipLaunchKernelGGL((bn2d::nhwc::rows_stats_k<T, L::VEC, L::AL>), grid, block, 0, st, X, M, (int)C, geo.lpr, geo.per, part);
   });
   bn2d::nhwc::launch_apply<true>(st, X, R, gamma, beta, M, (int)C, eps, momentum, slope, part, Y, save_mean, save_invstd, running_mean,
                                  running_var);
-  return launch_status("clica_bn2d_nhwc_act_fwd_train");
+  return launch_status(fn);
+}
+
+template <class T>
+int act_fwd_eval(const char* fn, const T* X, const T* R, const float* gamma, const float* beta, const float* running_mean,
+                 const float* running_var, int64_t M, int32_t C, float eps, float slope, T* Y, clica_stream_t stream) {
+  CLICA_BN2D_NHWC_SHAPE(fn, 1);
+  CLICA_BN2D_NHWC_SLOPE(fn);
+  CLICA_CHECK_ARG(X && gamma && beta && running_mean && running_var && Y, "%s: NULL pointer", fn);
+  // (the inference instance only reads the running statistics)
+  bn2d::nhwc::launch_apply<false>(as_stream(stream), X, R, gamma, beta, M, (int)C, eps, 0.f, slope, static_cast<const float*>(nullptr), Y,
+                                  static_cast<float*>(nullptr), static_cast<float*>(nullptr), const_cast<float*>(running_mean),
+                                  const_cast<float*>(running_var));
+  return launch_status(fn);
+}
+
+template <class T>
+int act_bwd(const char* fn, const T* X, const T* Y, const T* dY, const float* gamma, const float* save_mean, const float* save_invstd,
+            int64_t M, int32_t C, float slope, T* dX, T* dR, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
+            clica_stream_t stream) {
+  CLICA_BN2D_NHWC_SHAPE(fn, 2);
+  CLICA_BN2D_NHWC_SLOPE(fn);
+  CLICA_CHECK_ARG(X && Y && dY && gamma && save_mean && save_invstd && dX && dgamma && dbeta && workspace, "%s: NULL pointer", fn);
+  CLICA_BN2D_NHWC_WORKSPACE(fn, bn2d::rows_workspace_bytes(M, C), "clica_bn2d_nhwc_workspace_bytes", CLICA_E_INVALID);
+  const bn2d::Rows geo = bn2d::rows_geometry(M, C);
+  const dim3 sgrid((unsigned)geo.chunks, (unsigned)geo.S), agrid((unsigned)geo.chunks, (unsigned)geo.T), block(bn2d::kThreads);
+  hipStream_t st = as_stream(stream);
+  float* part = static_cast<float*>(workspace);
+  const bool al = lane_aligned(X) && lane_aligned(Y) && lane_aligned(dY) && lane_aligned(dX) && (!dR || lane_aligned(dR));
+  with_lane(geo.vec, al, [&](auto tag) {
+    using L = decltype(tag);
+    hipLaunchKernelGGL((bn2d::nhwc::rows_sums_k<T, L::VEC, L::AL>), sgrid, block, 0, st, X, Y, dY, save_mean, save_invstd, M, (int)C,
+                       geo.lpr, geo.per, slope, part);
+    hipLaunchKernelGGL((bn2d::nhwc::rows_bwd_apply_k<T, L::VEC, L::AL>), agrid, block, 0, st, X, Y, dY, gamma, save_mean, save_invstd, M,
+                       (int)C, geo.lpr, geo.mg, geo.ms, geo.S, geo.tile, (float)M, slope, part, dX, dR, dgamma, dbeta);
+  });
+  return launch_status(fn);
+}
+
+}  // namespace
+
+extern "C" int clica_bn2d_nhwc_act_fwd_train(const float* X, const float* R, const float* gamma, const float* beta, int64_t M, int32_t C,
+                                             float eps, float momentum, float slope, float* Y, float* save_mean, float* save_invstd,
+                                             float* running_mean, float* running_var, void* workspace, size_t workspace_bytes,
+                                             clica_stream_t stream) {
+  return act_fwd_train("clica_bn2d_nhwc_act_fwd_train", X, R, gamma, beta, M, C, eps, momentum, slope, Y, save_mean, save_invstd,
+                       running_mean, running_var, workspace, workspace_bytes, stream);
+}
+
+extern "C" int clica_bn2d_nhwc_act_fwd_train_bf16(const uint16_t* X, const uint16_t* R, const float* gamma, const float* beta, int64_t M,
+                                                  int32_t C, float eps, float momentum, float slope, uint16_t* Y, float* save_mean,
+                                                  float* save_invstd, float* running_mean, float* running_var, void* workspace,
+                                                  size_t workspace_bytes, clica_stream_t stream) {
+  return act_fwd_train("clica_bn2d_nhwc_act_fwd_train_bf16", X, R, gamma, beta, M, C, eps, momentum, slope, Y, save_mean, save_invstd,
+                       running_mean, running_var, workspace, workspace_bytes, stream);
 }
 
 extern "C" int clica_bn2d_nhwc_act_fwd_eval(const float* X, const float* R, const float* gamma, const float* beta, const float* running_mean,
                                             const float* running_var, int64_t M, int32_t C, float eps, float slope, float* Y,
                                             clica_stream_t stream) {
-  CLICA_BN2D_NHWC_SHAPE("clica_bn2d_nhwc_act_fwd_eval", 1);
-  CLICA_BN2D_NHWC_SLOPE("clica_bn2d_nhwc_act_fwd_eval");
-  CLICA_CHECK_ARG(X && gamma && beta && running_mean && running_var && Y, "clica_bn2d_nhwc_act_fwd_eval: NULL pointer");
-  // (the inference instance only reads the running statistics)
-  bn2d::nhwc::launch_apply<false>(as_stream(stream), X, R, gamma, beta, M, (int)C, eps, 0.f, slope, nullptr, Y, nullptr, nullptr,
-                                  const_cast<float*>(running_mean), const_cast<float*>(running_var));
-  return launch_status("clica_bn2d_nhwc_act_fwd_eval");
+  return act_fwd_eval("clica_bn2d_nhwc_act_fwd_eval", X, R, gamma, beta, running_mean, running_var, M, C, eps, slope, Y, stream);
+}
+
+extern "C" int clica_bn2d_nhwc_act_fwd_eval_bf16(const uint16_t* X, const uint16_t* R, const float* gamma, const float* beta,
+                                                 const float* running_mean, const float* running_var, int64_t M, int32_t C, float eps,
+                                                 float slope, uint16_t* Y, clica_stream_t stream) {
+  return act_fwd_eval("clica_bn2d_nhwc_act_fwd_eval_bf16", X, R, gamma, beta, running_mean, running_var, M, C, eps, slope, Y, stream);
 }
 
 extern "C" int clica_bn2d_nhwc_act_bwd(const float* X, const float* Y, const float* dY, const float* gamma, const float* save_mean,
                                        const float* save_invstd, int64_t M, int32_t C, float slope, float* dX, float* dR, float* dgamma,
                                        float* dbeta, void* workspace, size_t workspace_bytes, clica_stream_t stream) {
-  CLICA_BN2D_NHWC_SHAPE("clica_bn2d_nhwc_act_bwd", 2);
-  CLICA_BN2D_NHWC_SLOPE("clica_bn2d_nhwc_act_bwd");
-  CLICA_CHECK_ARG(X && Y && dY && gamma && save_mean && save_invstd && dX && dgamma && dbeta && workspace,
-                  "clica_bn2d_nhwc_act_bwd: NULL pointer");
-  CLICA_BN_WORKSPACE("clica_bn2d_nhwc_act_bwd", bn2d::rows_workspace_bytes(M, C), "clica_bn2d_nhwc_workspace_bytes", CLICA_E_INVALID);
-  const bn2d::Rows geo = bn2d::rows_geometry(M, C);
-  const dim3 sgrid((unsigned)geo.chunks, (unsigned)geo.S), agrid((unsigned)geo.chunks, (unsigned)geo.T), block(bn2d::kThreads);
-  hipStream_t st = as_stream(stream);
-  float* part = static_cast<float*>(workspace);
-  const bool al = bn2d::aligned16(X) && bn2d::aligned16(Y) && bn2d::aligned16(dY) && bn2d::aligned16(dX) && (!dR || bn2d::aligned16(dR));
-  with_lane(geo.vec, al, [&](auto tag) {
-    using T = decltype(tag);
-    hipLaunchKernelGGL((bn2d::nhwc::rows_sums_k<T::VEC, T::AL>), sgrid, block, 0, st, X, Y, dY, save_mean, save_invstd, M, (int)C, geo.lpr,
-                       geo.per, slope, part);
-    hipLaunchKernelGGL((bn2d::nhwc::rows_bwd_apply_k<T::VEC, T::AL>), agrid, block, 0, st, X, Y, dY, gamma, save_mean, save_invstd, M,
-                       (int)C, geo.lpr, geo.mg, geo.ms, geo.S, geo.tile, (float)M, slope, part, dX, dR, dgamma, dbeta);
-  });
-  return launch_status("clica_bn2d_nhwc_act_bwd");
+  return act_bwd("clica_bn2d_nhwc_act_bwd", X, Y, dY, gamma, save_mean, save_invstd, M, C, slope, dX, dR, dgamma, dbeta, workspace,
+                 workspace_bytes, stream);
+}
+
+extern "C" int clica_bn2d_nhwc_act_bwd_bf16(const uint16_t* X, const uint16_t* Y, const uint16_t* dY, const float* gamma,
+                                            const float* save_mean, const float* save_invstd, int64_t M, int32_t C, float slope,
+                                            uint16_t* dX, uint16_t* dR, float* dgamma, float* dbeta, void* workspace,
+                                            size_t workspace_bytes, clica_stream_t stream) {
+  return act_bwd("clica_bn2d_nhwc_act_bwd_bf16", X, Y, dY, gamma, save_mean, save_invstd, M, C, slope, dX, dR, dgamma, dbeta, workspace,
+                 workspace_bytes, stream);
 }
 
 #define CLICA_POOL_NHWC_SHAPE(fn, min_M)                                                                                                  \
   CLICA_CHECK_ARG(N >= 1 && N <= INT32_MAX && bn2d::pool_rows_fits(H, W, C) && (double)N * H * W >= (min_M) &&                            \
                       (double)N * (double)H * (double)W * (double)C < 1e18,                                                               \
-                  fn ": N=%lld C=%d H=%d W=%d (N >= 1, 1 <= C <= %d, 1 <= H, W <= %d, N H W >= %d)", (long long)N, C, H, W, bn2d::kMaxC,  \
-                  bn2d::kPoolRowsMaxSide, (min_M))
+                  "%s: N=%lld C=%d H=%d W=%d (N >= 1, 1 <= C <= %d, 1 <= H, W <= %d, N H W >= %d)", fn, (long long)N, C, H, W,            \
+                  bn2d::kMaxC, bn2d::kPoolRowsMaxSide, (min_M))
 
 // (as pool2d.hip's: the pool's argmax is taken after the activation)
-#define CLICA_POOL_NHWC_SLOPE(fn) CLICA_CHECK_ARG(slope >= 0.f && slope <= 1.f, fn ": slope=%g must be in [0, 1]", slope)
+#define CLICA_POOL_NHWC_SLOPE(fn) CLICA_CHECK_ARG(slope >= 0.f && slope <= 1.f, "%s: slope=%g must be in [0, 1]", fn, slope)
 
 #define CLICA_POOL_NHWC_WORKSPACE(fn) \
-  CLICA_BN_WORKSPACE(fn, bn2d::pool_rows_workspace_bytes(N, C, H, W), "clica_bn2d_nhwc_maxpool_workspace_bytes", CLICA_E_WORKSPACE)
+  CLICA_BN2D_NHWC_WORKSPACE(fn, bn2d::pool_rows_workspace_bytes(N, C, H, W), "clica_bn2d_nhwc_maxpool_workspace_bytes", CLICA_E_WORKSPACE)
 
 extern "C" int clica_bn2d_nhwc_maxpool_workspace_bytes(int64_t N, int32_t C, int32_t H, int32_t W, size_t* bytes) {
   CLICA_CHECK_ARG(bytes != nullptr, "clica_bn2d_nhwc_maxpool_workspace_bytes: bytes is NULL");
@@ -729,86 +799,160 @@ extern "C" int clica_bn2d_nhwc_maxpool_workspace_bytes(int64_t N, int32_t C, int
   return CLICA_OK;
 }
 
-extern "C" int clica_bn2d_nhwc_act_maxpool_fwd_train(const float* X, const float* gamma, const float* beta, int64_t N, int32_t C, int32_t H,
-                                                     int32_t W, float eps, float momentum, float slope, float* P, float* save_mean,
-                                                     float* save_invstd, float* running_mean, float* running_var, void* workspace,
-                                                     size_t workspace_bytes, clica_stream_t stream) {
-  CLICA_POOL_NHWC_SHAPE("clica_bn2d_nhwc_act_maxpool_fwd_train", 2);
-  CLICA_POOL_NHWC_SLOPE("clica_bn2d_nhwc_act_maxpool_fwd_train");
-  CLICA_CHECK_ARG(X && gamma && beta && P && save_mean && save_invstd && workspace, "clica_bn2d_nhwc_act_maxpool_fwd_train: NULL pointer");
-  CLICA_POOL_NHWC_WORKSPACE("clica_bn2d_nhwc_act_maxpool_fwd_train");
+namespace {
+
+template <class T>
+int act_maxpool_fwd_train(const char* fn, const T* X, const float* gamma, const float* beta, int64_t N, int32_t C, int32_t H, int32_t W,
+                          float eps, float momentum, float slope, T* P, float* save_mean, float* save_invstd, float* running_mean,
+                          float* running_var, void* workspace, size_t workspace_bytes, clica_stream_t stream) {
+  CLICA_POOL_NHWC_SHAPE(fn, 2);
+  CLICA_POOL_NHWC_SLOPE(fn);
+  CLICA_CHECK_ARG(X && gamma && beta && P && save_mean && save_invstd && workspace, "%s: NULL pointer", fn);
+  CLICA_POOL_NHWC_WORKSPACE(fn);
   hipStream_t st = as_stream(stream);
   float* part = static_cast<float*>(workspace);
   const int64_t M = N * H * W;
   const bn2d::Rows geo = bn2d::rows_geometry(M, C);          // the unit's statistics launch: its partials, its bits
   const dim3 grid((unsigned)geo.chunks, (unsigned)geo.S), block(bn2d::kThreads);
-  with_lane(geo.vec, bn2d::aligned16(X), [&](auto tag) {
-    using T = decltype(tag);
-    hipLaunchKernelGGL((bn2d::nhwc::rows_stats_k<T::VEC, T::AL>), grid, block, 0, st, X, M, (int)C, geo.lpr, geo.per, part);
+  with_lane(geo.vec, lane_aligned(X), [&](auto tag) {
+    using L = decltype(tag);
+    hipLaunchKernelGGL((bn2d::nhwc::rows_stats_k<T, L::VEC, L::AL>), grid, block, 0, st, X, M, (int)C, geo.lpr, geo.per, part);
   });
   bn2d::nhwc::launch_pool_fwd<true>(st, X, gamma, beta, N, (int)C, (int)H, (int)W, eps, momentum, slope, part, P, save_mean, save_invstd,
                                     running_mean, running_var);
-  return launch_status("clica_bn2d_nhwc_act_maxpool_fwd_train");
+  return launch_status(fn);
 }
 
-extern "C" int clica_bn2d_nhwc_act_maxpool_fwd_eval(const float* X, const float* gamma, const float* beta, const float* running_mean,
-                                                    const float* running_var, int64_t N, int32_t C, int32_t H, int32_t W, float eps,
-                                                    float slope, float* P, clica_stream_t stream) {
-  CLICA_POOL_NHWC_SHAPE("clica_bn2d_nhwc_act_maxpool_fwd_eval", 1);
-  CLICA_POOL_NHWC_SLOPE("clica_bn2d_nhwc_act_maxpool_fwd_eval");
-  CLICA_CHECK_ARG(X && gamma && beta && running_mean && running_var && P, "clica_bn2d_nhwc_act_maxpool_fwd_eval: NULL pointer");
+template <class T>
+int act_maxpool_fwd_eval(const char* fn, const T* X, const float* gamma, const float* beta, const float* running_mean,
+                         const float* running_var, int64_t N, int32_t C, int32_t H, int32_t W, float eps, float slope, T* P,
+                         clica_stream_t stream) {
+  CLICA_POOL_NHWC_SHAPE(fn, 1);
+  CLICA_POOL_NHWC_SLOPE(fn);
+  CLICA_CHECK_ARG(X && gamma && beta && running_mean && running_var && P, "%s: NULL pointer", fn);
   // (the inference instance only reads the running statistics)
-  bn2d::nhwc::launch_pool_fwd<false>(as_stream(stream), X, gamma, beta, N, (int)C, (int)H, (int)W, eps, 0.f, slope, nullptr, P, nullptr,
-                                     nullptr, const_cast<float*>(running_mean), const_cast<float*>(running_var));
-  return launch_status("clica_bn2d_nhwc_act_maxpool_fwd_eval");
+  bn2d::nhwc::launch_pool_fwd<false>(as_stream(stream), X, gamma, beta, N, (int)C, (int)H, (int)W, eps, 0.f, slope,
+                                     static_cast<const float*>(nullptr), P, static_cast<float*>(nullptr), static_cast<float*>(nullptr),
+                                     const_cast<float*>(running_mean), const_cast<float*>(running_var));
+  return launch_status(fn);
 }
 
-extern "C" int clica_bn2d_nhwc_act_maxpool_bwd(const float* X, const float* dP, const float* gamma, const float* beta, const float* save_mean,
-                                               const float* save_invstd, int64_t N, int32_t C, int32_t H, int32_t W, float slope, float* dX,
-                                               float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, clica_stream_t stream) {
-  CLICA_POOL_NHWC_SHAPE("clica_bn2d_nhwc_act_maxpool_bwd", 2);
-  CLICA_POOL_NHWC_SLOPE("clica_bn2d_nhwc_act_maxpool_bwd");
-  CLICA_CHECK_ARG(X && dP && gamma && beta && save_mean && save_invstd && dX && dgamma && dbeta && workspace,
-                  "clica_bn2d_nhwc_act_maxpool_bwd: NULL pointer");
-  CLICA_POOL_NHWC_WORKSPACE("clica_bn2d_nhwc_act_maxpool_bwd");
+template <class T>
+int act_maxpool_bwd(const char* fn, const T* X, const T* dP, const float* gamma, const float* beta, const float* save_mean,
+                    const float* save_invstd, int64_t N, int32_t C, int32_t H, int32_t W, float slope, T* dX, float* dgamma, float* dbeta,
+                    void* workspace, size_t workspace_bytes, clica_stream_t stream) {
+  CLICA_POOL_NHWC_SHAPE(fn, 2);
+  CLICA_POOL_NHWC_SLOPE(fn);
+  CLICA_CHECK_ARG(X && dP && gamma && beta && save_mean && save_invstd && dX && dgamma && dbeta && workspace, "%s: NULL pointer", fn);
+  CLICA_POOL_NHWC_WORKSPACE(fn);
   const bn2d::PoolRows geo = bn2d::pool_rows_geometry(N, C, H, W);
   const bn2d::Rows& r = geo.rows;
   const bn2d::nhwc::PoolPlane plane{(int)H, (int)W, (int)C, geo.Ho, geo.Wo, geo.BH, geo.BW, geo.nbh, geo.nbw};
   const dim3 sgrid((unsigned)r.chunks, (unsigned)geo.Sb), agrid((unsigned)r.chunks, (unsigned)geo.Ta), block(bn2d::kThreads);
   hipStream_t st = as_stream(stream);
   float* part = static_cast<float*>(workspace);
-  const bool al = bn2d::aligned16(X) && bn2d::aligned16(dP) && bn2d::aligned16(dX);
+  const bool al = lane_aligned(X) && lane_aligned(dP) && lane_aligned(dX);
   with_lane(r.vec, al, [&](auto tag) {
-    using T = decltype(tag);
-    hipLaunchKernelGGL((bn2d::nhwc::pool_rows_sums_k<T::VEC, T::AL>), sgrid, block, 0, st, X, dP, gamma, beta, save_mean, save_invstd,
+    using L = decltype(tag);
+    hipLaunchKernelGGL((bn2d::nhwc::pool_rows_sums_k<T, L::VEC, L::AL>), sgrid, block, 0, st, X, dP, gamma, beta, save_mean, save_invstd,
                        N * geo.Ho * geo.Wo, (int)C, (int)H, (int)W, geo.Ho, geo.Wo, r.lpr, geo.per_b, slope, part);
-    hipLaunchKernelGGL((bn2d::nhwc::pool_rows_bwd_apply_k<T::VEC, T::AL>), agrid, block, 0, st, X, dP, gamma, beta, save_mean, save_invstd,
-                       plane, r.lpr, r.mg, geo.msb, geo.Sb, geo.tiles, geo.per_a, (float)(N * H * W), slope, part, dX, dgamma, dbeta);
+    hipLaunchKernelGGL((bn2d::nhwc::pool_rows_bwd_apply_k<T, L::VEC, L::AL>), agrid, block, 0, st, X, dP, gamma, beta, save_mean,
+                       save_invstd, plane, r.lpr, r.mg, geo.msb, geo.Sb, geo.tiles, geo.per_a, (float)(N * H * W), slope, part, dX, dgamma,
+                       dbeta);
   });
-  return launch_status("clica_bn2d_nhwc_act_maxpool_bwd");
+  return launch_status(fn);
+}
+
+}  // namespace
+
+extern "C" int clica_bn2d_nhwc_act_maxpool_fwd_train(const float* X, const float* gamma, const float* beta, int64_t N, int32_t C, int32_t H,
+                                                     int32_t W, float eps, float momentum, float slope, float* P, float* save_mean,
+                                                     float* save_invstd, float* running_mean, float* running_var, void* workspace,
+                                                     size_t workspace_bytes, clica_stream_t stream) {
+  return act_maxpool_fwd_train("clica_bn2d_nhwc_act_maxpool_fwd_train", X, gamma, beta, N, C, H, W, eps, momentum, slope, P, save_mean,
+                               save_invstd, running_mean, running_var, workspace, workspace_bytes, stream);
+}
+
+extern "C" int clica_bn2d_nhwc_act_maxpool_fwd_train_bf16(const uint16_t* X, const float* gamma, const float* beta, int64_t N, int32_t C,
+                                                          int32_t H, int32_t W, float eps, float momentum, float slope, uint16_t* P,
+                                                          float* save_mean, float* save_invstd, float* running_mean, float* running_var,
+                                                          void* workspace, size_t workspace_bytes, clica_stream_t stream) {
+  return act_maxpool_fwd_train("clica_bn2d_nhwc_act_maxpool_fwd_train_bf16", X, gamma, beta, N, C, H, W, eps, momentum, slope, P, save_mean,
+                               save_invstd, running_mean, running_var, workspace, workspace_bytes, stream);
+}
+
+extern "C" int clica_bn2d_nhwc_act_maxpool_fwd_eval(const float* X, const float* gamma, const float* beta, const float* running_mean,
+                                                    const float* running_var, int64_t N, int32_t C, int32_t H, int32_t W, float eps,
+                                                    float slope, float* P, clica_stream_t stream) {
+  return act_maxpool_fwd_eval("clica_bn2d_nhwc_act_maxpool_fwd_eval", X, gamma, beta, running_mean, running_var, N, C, H, W, eps, slope, P,
+                              stream);
+}
+
+extern "C" int clica_bn2d_nhwc_act_maxpool_fwd_eval_bf16(const uint16_t* X, const float* gamma, const float* beta, const float* running_mean,
+                                                         const float* running_var, int64_t N, int32_t C, int32_t H, int32_t W, float eps,
+                                                         float slope, uint16_t* P, clica_stream_t stream) {
+  return act_maxpool_fwd_eval("clica_bn2d_nhwc_act_maxpool_fwd_eval_bf16", X, gamma, beta, running_mean, running_var, N, C, H, W, eps,
+                              slope, P, stream);
+}
+
+extern "C" int clica_bn2d_nhwc_act_maxpool_bwd(const float* X, const float* dP, const float* gamma, const float* beta, const float* save_mean,
+                                               const float* save_invstd, int64_t N, int32_t C, int32_t H, int32_t W, float slope, float* dX,
+                                               float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, clica_stream_t stream) {
+  return act_maxpool_bwd("clica_bn2d_nhwc_act_maxpool_bwd", X, dP, gamma, beta, save_mean, save_invstd, N, C, H, W, slope, dX, dgamma,
+                         dbeta, workspace, workspace_bytes, stream);
+}
+
+extern "C" int clica_bn2d_nhwc_act_maxpool_bwd_bf16(const uint16_t* X, const uint16_t* dP, const float* gamma, const float* beta,
+                                                    const float* save_mean, const float* save_invstd, int64_t N, int32_t C, int32_t H,
+                                                    int32_t W, float slope, uint16_t* dX, float* dgamma, float* dbeta, void* workspace,
+                                                    size_t workspace_bytes, clica_stream_t stream) {
+  return act_maxpool_bwd("clica_bn2d_nhwc_act_maxpool_bwd_bf16", X, dP, gamma, beta, save_mean, save_invstd, N, C, H, W, slope, dX, dgamma,
+                         dbeta, workspace, workspace_bytes, stream);
 }
 
 // (the limits of clica_avgpool2d_global_*: pool2d.hip)
 #define CLICA_AVGPOOL_NHWC_SHAPE(fn)                                                                                                  \
   CLICA_CHECK_ARG(N >= 1 && HW >= 1 && HW <= (1 << 14) && C >= 1 && C <= bn2d::kMaxC && N * (int64_t)C <= ((int64_t)1 << 31) &&      \
                       (double)N * (double)HW * (double)C <= 274877906944.0,                                                          \
-                  fn ": N=%lld HW=%d C=%d (N >= 1, 1 <= HW <= 16384, 1 <= C <= %d, N C <= 2^31, N HW C <= 2^38)", (long long)N, HW, C, \
-                  bn2d::kMaxC)
+                  "%s: N=%lld HW=%d C=%d (N >= 1, 1 <= HW <= 16384, 1 <= C <= %d, N C <= 2^31, N HW C <= 2^38)", fn, (long long)N, HW, \
+                  C, bn2d::kMaxC)
 
-extern "C" int clica_avgpool2d_global_nhwc_fwd(const float* X, int64_t N, int32_t HW, int32_t C, float* Y, clica_stream_t stream) {
-  CLICA_AVGPOOL_NHWC_SHAPE("clica_avgpool2d_global_nhwc_fwd");
-  CLICA_CHECK_ARG(X && Y, "clica_avgpool2d_global_nhwc_fwd: NULL pointer");
+namespace {
+
+template <class T>
+int avgpool_fwd(const char* fn, const T* X, int64_t N, int32_t HW, int32_t C, float* Y, clica_stream_t stream) {
+  CLICA_AVGPOOL_NHWC_SHAPE(fn);
+  CLICA_CHECK_ARG(X && Y, "%s: NULL pointer", fn);
   const int64_t NC = N * C;
   const dim3 grid((unsigned)ceil_div(NC, bn2d::kThreads)), block(bn2d::kThreads);
-  hipLaunchKernelGGL(bn2d::nhwc::avgpool_fwd_k, grid, block, 0, as_stream(stream), X, NC, (int)HW, (int)C, 1.f / (float)HW, Y);
-  return launch_status("clica_avgpool2d_global_nhwc_fwd");
+  hipLaunchKernelGGL(bn2d::nhwc::avgpool_fwd_k<T>, grid, block, 0, as_stream(stream), X, NC, (int)HW, (int)C, 1.f / (float)HW, Y);
+  return launch_status(fn);
+}
+
+template <class T>
+int avgpool_bwd(const char* fn, const float* dY, int64_t N, int32_t HW, int32_t C, T* dX, clica_stream_t stream) {
+  CLICA_AVGPOOL_NHWC_SHAPE(fn);
+  CLICA_CHECK_ARG(dY && dX, "%s: NULL pointer", fn);
+  const int64_t total = N * HW * C;
+  const dim3 grid((unsigned)ceil_div(total, bn2d::kThreads)), block(bn2d::kThreads);
+  hipLaunchKernelGGL(bn2d::nhwc::avgpool_bwd_k<T>, grid, block, 0, as_stream(stream), dY, total, (int)HW, (int)C, 1.f / (float)HW, dX);
+  return launch_status(fn);
+}
+
+}  // namespace
+
+extern "C" int clica_avgpool2d_global_nhwc_fwd(const float* X, int64_t N, int32_t HW, int32_t C, float* Y, clica_stream_t stream) {
+  return avgpool_fwd("clica_avgpool2d_global_nhwc_fwd", X, N, HW, C, Y, stream);
+}
+
+extern "C" int clica_avgpool2d_global_nhwc_fwd_bf16(const uint16_t* X, int64_t N, int32_t HW, int32_t C, float* Y, clica_stream_t stream) {
+  return avgpool_fwd("clica_avgpool2d_global_nhwc_fwd_bf16", X, N, HW, C, Y, stream);
 }
 
 extern "C" int clica_avgpool2d_global_nhwc_bwd(const float* dY, int64_t N, int32_t HW, int32_t C, float* dX, clica_stream_t stream) {
-  CLICA_AVGPOOL_NHWC_SHAPE("clica_avgpool2d_global_nhwc_bwd");
-  CLICA_CHECK_ARG(dY && dX, "clica_avgpool2d_global_nhwc_bwd: NULL pointer");
-  const int64_t total = N * HW * C;
-  const dim3 grid((unsigned)ceil_div(total, bn2d::kThreads)), block(bn2d::kThreads);
-  hipLaunchKernelGGL(bn2d::nhwc::avgpool_bwd_k, grid, block, 0, as_stream(stream), dY, total, (int)HW, (int)C, 1.f / (float)HW, dX);
-  return launch_status("clica_avgpool2d_global_nhwc_bwd");
+  return avgpool_bwd("clica_avgpool2d_global_nhwc_bwd", dY, N, HW, C, dX, stream);
+}
+
+extern "C" int clica_avgpool2d_global_nhwc_bwd_bf16(const float* dY, int64_t N, int32_t HW, int32_t C, uint16_t* dX, clica_stream_t stream) {
+  return avgpool_bwd("clica_avgpool2d_global_nhwc_bwd_bf16", dY, N, HW, C, dX, stream);
 }

@@ -64,7 +64,7 @@ extern "C" int clica_clock_probe(unsigned long long* samples, int32_t n, int32_t
 }
 
 extern "C" const char* clica_last_error(void) { return clica::g_err; }
-extern "C" int clica_version(void) { return 101; }
+extern "C" int clica_version(void) { return 102; }
 
 extern "C" int clica_stamp(unsigned long long* slot, int32_t which, int32_t capacity, clica_stream_t stream) {
   CLICA_CHECK_ARG(slot != nullptr && capacity >= 1 && (which == 0 || which == 1), "clica_stamp: bad argument");

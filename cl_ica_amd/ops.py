@@ -1070,17 +1070,40 @@ class _Bn2dLayout(NamedTuple):
     bwd: str
     pool_fwd: str
     pool_bwd: str
+    bf16: bool                                  # are there `name + "_bf16"` entry points for bf16 activations?
 
-    def empty(self, shape, device) -> torch.Tensor:
-        return torch.empty(tuple(shape), dtype=torch.float32, device=device, memory_format=self.memory_format)
+    def empty(self, shape, device, dtype=torch.float32) -> torch.Tensor:
+        return torch.empty(tuple(shape), dtype=dtype, device=device, memory_format=self.memory_format)
 
 
 _NCHW = _Bn2dLayout(_bn2d_map, torch.contiguous_format, lambda N, n, H, W: (N, n, H * W), lambda N, n, H, W: (N * n, H * W), bn2d_workspace,
                     "clica_bn2d_act_fwd_train", "clica_bn2d_act_fwd_eval", "clica_bn2d_act_bwd",
-                    "clica_avgpool2d_global_fwd", "clica_avgpool2d_global_bwd")
+                    "clica_avgpool2d_global_fwd", "clica_avgpool2d_global_bwd", False)
 _NHWC = _Bn2dLayout(_bn2d_nhwc_map, torch.channels_last, lambda N, n, H, W: (N * H * W, n), lambda N, n, H, W: (N, H * W, n), bn2d_nhwc_workspace,
                     "clica_bn2d_nhwc_act_fwd_train", "clica_bn2d_nhwc_act_fwd_eval", "clica_bn2d_nhwc_act_bwd",
-                    "clica_avgpool2d_global_nhwc_fwd", "clica_avgpool2d_global_nhwc_bwd")
+                    "clica_avgpool2d_global_nhwc_fwd", "clica_avgpool2d_global_nhwc_bwd", True)
+
+
+def _acts_on_gpu(L, **acts) -> torch.dtype:
+    """The activations of one call (None: absent) live on the GPU and share one element type, which is returned: float32, or bfloat16
+    where the layout has kernels for it.  Anything else raises before any launch -- a bf16 x with an fp32 residual or dy among it."""
+    named = [(name, t) for name, t in acts.items() if t is not None]
+    lead, dtype = named[0][0], named[0][1].dtype
+    if not (L.bf16 and dtype == torch.bfloat16):
+        _on_gpu(**acts)
+        return torch.float32
+    for name, t in named:
+        if not t.is_cuda:
+            raise ClicaError(f"{name} must live on the GPU (got device {t.device}); cl_ica_amd runs only through its HIP kernels")
+        if t.dtype != dtype:
+            raise ClicaError(f"{name} must be {dtype} as {lead} is (got {t.dtype}): the activations of a call share one element type")
+    return dtype
+
+
+def _entry(name: str, dtype: torch.dtype):
+    """The entry point `name` for activations of `dtype` (what _acts_on_gpu returned)."""
+    name = name + "_bf16" if dtype == torch.bfloat16 else name
+    return getattr(load(), name), name
 
 
 def _bn2d_act_fwd(L, x, weight, bias, running_mean, running_var, eps, momentum, slope, residual):
@@ -1090,15 +1113,16 @@ def _bn2d_act_fwd(L, x, weight, bias, running_mean, running_var, eps, momentum, 
         L.map("residual", residual, x.shape)
     _running_pair(running_mean, running_var)
     _norm_vecs(n, weight=weight, bias=bias, running_mean=running_mean, running_var=running_var)
-    _on_gpu(x=x, residual=residual, weight=weight, bias=bias, running_mean=running_mean, running_var=running_var)
+    dtype = _acts_on_gpu(L, x=x, residual=residual)
+    _on_gpu(weight=weight, bias=bias, running_mean=running_mean, running_var=running_var)
     dims = L.unit_dims(*x.shape)
     ws = L.workspace(*dims, x.device)       # (validates the shape; one value per channel is the training call's to refuse)
-    y = L.empty(x.shape, x.device)
+    y = L.empty(x.shape, x.device, dtype)
     save_mean = torch.empty(n, dtype=torch.float32, device=x.device)
     save_invstd = torch.empty(n, dtype=torch.float32, device=x.device)
-    check(getattr(load(), L.fwd_train)(x.data_ptr(), ptr(residual), weight.data_ptr(), bias.data_ptr(), *dims, float(eps), float(momentum),
-                                       float(slope), y.data_ptr(), save_mean.data_ptr(), save_invstd.data_ptr(), ptr(running_mean),
-                                       ptr(running_var), ws.data_ptr(), ws.numel(), stream_ptr()), L.fwd_train)
+    fn, name = _entry(L.fwd_train, dtype)
+    check(fn(x.data_ptr(), ptr(residual), weight.data_ptr(), bias.data_ptr(), *dims, float(eps), float(momentum), float(slope), y.data_ptr(),
+             save_mean.data_ptr(), save_invstd.data_ptr(), ptr(running_mean), ptr(running_var), ws.data_ptr(), ws.numel(), stream_ptr()), name)
     return y, save_mean, save_invstd
 
 
@@ -1107,11 +1131,12 @@ def _bn2d_act_eval(L, x, weight, bias, running_mean, running_var, eps, slope, re
     if residual is not None:
         L.map("residual", residual, x.shape)
     _norm_vecs(x.shape[1], weight=weight, bias=bias, running_mean=running_mean, running_var=running_var)
-    _on_gpu(x=x, residual=residual, weight=weight, bias=bias, running_mean=running_mean, running_var=running_var)
-    y = L.empty(x.shape, x.device)
-    check(getattr(load(), L.fwd_eval)(x.data_ptr(), ptr(residual), weight.data_ptr(), bias.data_ptr(), running_mean.data_ptr(),
-                                      running_var.data_ptr(), *L.unit_dims(*x.shape), float(eps), float(slope), y.data_ptr(), stream_ptr()),
-          L.fwd_eval)
+    dtype = _acts_on_gpu(L, x=x, residual=residual)
+    _on_gpu(weight=weight, bias=bias, running_mean=running_mean, running_var=running_var)
+    y = L.empty(x.shape, x.device, dtype)
+    fn, name = _entry(L.fwd_eval, dtype)
+    check(fn(x.data_ptr(), ptr(residual), weight.data_ptr(), bias.data_ptr(), running_mean.data_ptr(), running_var.data_ptr(),
+             *L.unit_dims(*x.shape), float(eps), float(slope), y.data_ptr(), stream_ptr()), name)
     return y
 
 
@@ -1120,34 +1145,39 @@ def _bn2d_act_bwd(L, x, y, dy, weight, save_mean, save_invstd, slope, need_dr):
     L.map("y", y, x.shape); L.map("dy", dy, x.shape)
     n = x.shape[1]
     _norm_vecs(n, weight=weight, save_mean=save_mean, save_invstd=save_invstd)
-    _on_gpu(x=x, y=y, dy=dy, weight=weight, save_mean=save_mean, save_invstd=save_invstd)
+    dtype = _acts_on_gpu(L, x=x, y=y, dy=dy)
+    _on_gpu(weight=weight, save_mean=save_mean, save_invstd=save_invstd)
     dims = L.unit_dims(*x.shape)
     ws = L.workspace(*dims, x.device)
-    dx = L.empty(x.shape, x.device)
-    dr = L.empty(x.shape, x.device) if need_dr else None
+    dx = L.empty(x.shape, x.device, dtype)
+    dr = L.empty(x.shape, x.device, dtype) if need_dr else None
     dw = torch.empty(n, dtype=torch.float32, device=x.device)
     db = torch.empty(n, dtype=torch.float32, device=x.device)
-    check(getattr(load(), L.bwd)(x.data_ptr(), y.data_ptr(), dy.data_ptr(), weight.data_ptr(), save_mean.data_ptr(), save_invstd.data_ptr(),
-                                 *dims, float(slope), dx.data_ptr(), ptr(dr), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(),
-                                 stream_ptr()), L.bwd)
+    fn, name = _entry(L.bwd, dtype)
+    check(fn(x.data_ptr(), y.data_ptr(), dy.data_ptr(), weight.data_ptr(), save_mean.data_ptr(), save_invstd.data_ptr(), *dims, float(slope),
+             dx.data_ptr(), ptr(dr), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()), name)
     return dx, dr, dw, db
 
 
 def _avgpool2d_global_fwd(L, x):
     x = L.map("x", x)
-    _on_gpu(x=x)
+    dtype = _acts_on_gpu(L, x=x)
     y = torch.empty(tuple(x.shape[:2]), dtype=torch.float32, device=x.device)
-    check(getattr(load(), L.pool_fwd)(x.data_ptr(), *L.pool_dims(*x.shape), y.data_ptr(), stream_ptr()), L.pool_fwd)
+    fn, name = _entry(L.pool_fwd, dtype)
+    check(fn(x.data_ptr(), *L.pool_dims(*x.shape), y.data_ptr(), stream_ptr()), name)
     return y
 
 
-def _avgpool2d_global_bwd(L, dy, H, W):
+def _avgpool2d_global_bwd(L, dy, H, W, dtype=torch.float32):
     if dy.dim() != 2 or not dy.is_contiguous():
         raise ValueError(f"dy must be a contiguous matrix [N, C], got shape {tuple(dy.shape)} strides {dy.stride()}")
     _on_gpu(dy=dy)
     shape = tuple(dy.shape) + (int(H), int(W))
-    dx = L.empty(shape, dy.device)
-    check(getattr(load(), L.pool_bwd)(dy.data_ptr(), *L.pool_dims(*shape), dx.data_ptr(), stream_ptr()), L.pool_bwd)
+    if dtype != torch.float32 and not (L.bf16 and dtype == torch.bfloat16):
+        raise ClicaError(f"dx can be float32{' or bfloat16' if L.bf16 else ''}, not {dtype}")
+    dx = L.empty(shape, dy.device, dtype)
+    fn, name = _entry(L.pool_bwd, dtype)
+    check(fn(dy.data_ptr(), *L.pool_dims(*shape), dx.data_ptr(), stream_ptr()), name)
     return dx
 
 
@@ -1185,7 +1215,10 @@ def batchnorm2d_act_fwd_nhwc(x, weight, bias, running_mean=None, running_var=Non
                              slope: float = 0.0, residual=None):
     """batchnorm2d_act_fwd on a dense channels-last x (N H W >= 2) and residual: two launches (clica_bn2d_nhwc_act_fwd_train).
     Returns (y, save_mean [C], save_invstd [C]), y channels-last.  Anything but dense channels-last maps of one shape and vectors of C
-    values: ValueError, before any launch."""
+    values: ValueError, before any launch.
+    This and the other ``*_nhwc`` functions also take bf16 ACTIVATIONS (x, residual, y, dy, dp) -- all of one call alike, or ClicaError --
+    and then run the ``_bf16`` entry points: outputs shaped like x and input gradients are bf16, rounded to nearest even from what the
+    fp32 call computes on the upcast activations; parameters, statistics, their gradients and the average pool's [N, C] matrix are fp32."""
     return _bn2d_act_fwd(_NHWC, x, weight, bias, running_mean, running_var, eps, momentum, slope, residual)
 
 
@@ -1205,9 +1238,10 @@ def avgpool2d_global_fwd_nhwc(x):
     return _avgpool2d_global_fwd(_NHWC, x)
 
 
-def avgpool2d_global_bwd_nhwc(dy, H: int, W: int):
-    """dx [N, C, H, W], dense channels-last, = dy [N, C] / (H W) on every pixel: one launch (clica_avgpool2d_global_nhwc_bwd)."""
-    return _avgpool2d_global_bwd(_NHWC, dy, H, W)
+def avgpool2d_global_bwd_nhwc(dy, H: int, W: int, dtype=torch.float32):
+    """dx [N, C, H, W], dense channels-last, = dy [N, C] / (H W) on every pixel: one launch (clica_avgpool2d_global_nhwc_bwd).  dy is
+    fp32; `dtype` (that of the forward's x: float32 or bfloat16) is dx's."""
+    return _avgpool2d_global_bwd(_NHWC, dy, H, W, dtype)
 
 
 # ------------------------------------------------------------------------------- the stem unit with its max-pool, contiguous NCHW
@@ -1311,15 +1345,15 @@ def batchnorm2d_act_maxpool_fwd_nhwc(x, weight, bias, running_mean=None, running
     N, n, H, W = x.shape
     _running_pair(running_mean, running_var)
     _norm_vecs(n, weight=weight, bias=bias, running_mean=running_mean, running_var=running_var)
-    _on_gpu(x=x, weight=weight, bias=bias, running_mean=running_mean, running_var=running_var)
+    dtype = _acts_on_gpu(_NHWC, x=x)
+    _on_gpu(weight=weight, bias=bias, running_mean=running_mean, running_var=running_var)
     ws = bn2d_nhwc_maxpool_workspace(N, n, H, W, x.device)       # (validates the shape)
-    p = _NHWC.empty((N, n) + maxpool_out_hw(H, W), x.device)
+    p = _NHWC.empty((N, n) + maxpool_out_hw(H, W), x.device, dtype)
     save_mean = torch.empty(n, dtype=torch.float32, device=x.device)
     save_invstd = torch.empty(n, dtype=torch.float32, device=x.device)
-    check(load().clica_bn2d_nhwc_act_maxpool_fwd_train(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), N, n, H, W, float(eps),
-                                                       float(momentum), float(slope), p.data_ptr(), save_mean.data_ptr(),
-                                                       save_invstd.data_ptr(), ptr(running_mean), ptr(running_var), ws.data_ptr(),
-                                                       ws.numel(), stream_ptr()), "clica_bn2d_nhwc_act_maxpool_fwd_train")
+    fn, name = _entry("clica_bn2d_nhwc_act_maxpool_fwd_train", dtype)
+    check(fn(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), N, n, H, W, float(eps), float(momentum), float(slope), p.data_ptr(),
+             save_mean.data_ptr(), save_invstd.data_ptr(), ptr(running_mean), ptr(running_var), ws.data_ptr(), ws.numel(), stream_ptr()), name)
     return p, save_mean, save_invstd
 
 
@@ -1328,11 +1362,12 @@ def batchnorm2d_act_maxpool_eval_nhwc(x, weight, bias, running_mean, running_var
     x = _bn2d_nhwc_map("x", x)
     N, n, H, W = x.shape
     _norm_vecs(n, weight=weight, bias=bias, running_mean=running_mean, running_var=running_var)
-    _on_gpu(x=x, weight=weight, bias=bias, running_mean=running_mean, running_var=running_var)
-    p = _NHWC.empty((N, n) + maxpool_out_hw(H, W), x.device)
-    check(load().clica_bn2d_nhwc_act_maxpool_fwd_eval(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), running_mean.data_ptr(),
-                                                      running_var.data_ptr(), N, n, H, W, float(eps), float(slope), p.data_ptr(),
-                                                      stream_ptr()), "clica_bn2d_nhwc_act_maxpool_fwd_eval")
+    dtype = _acts_on_gpu(_NHWC, x=x)
+    _on_gpu(weight=weight, bias=bias, running_mean=running_mean, running_var=running_var)
+    p = _NHWC.empty((N, n) + maxpool_out_hw(H, W), x.device, dtype)
+    fn, name = _entry("clica_bn2d_nhwc_act_maxpool_fwd_eval", dtype)
+    check(fn(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), running_mean.data_ptr(), running_var.data_ptr(), N, n, H, W, float(eps),
+             float(slope), p.data_ptr(), stream_ptr()), name)
     return p
 
 
@@ -1343,14 +1378,15 @@ def batchnorm2d_act_maxpool_bwd_nhwc(x, dp, weight, bias, save_mean, save_invstd
     N, n, H, W = x.shape
     _bn2d_nhwc_map("dp", dp, (N, n) + maxpool_out_hw(H, W))
     _norm_vecs(n, weight=weight, bias=bias, save_mean=save_mean, save_invstd=save_invstd)
-    _on_gpu(x=x, dp=dp, weight=weight, bias=bias, save_mean=save_mean, save_invstd=save_invstd)
+    dtype = _acts_on_gpu(_NHWC, x=x, dp=dp)
+    _on_gpu(weight=weight, bias=bias, save_mean=save_mean, save_invstd=save_invstd)
     ws = bn2d_nhwc_maxpool_workspace(N, n, H, W, x.device)
-    dx = _NHWC.empty(x.shape, x.device)
+    dx = _NHWC.empty(x.shape, x.device, dtype)
     dw = torch.empty(n, dtype=torch.float32, device=x.device)
     db = torch.empty(n, dtype=torch.float32, device=x.device)
-    check(load().clica_bn2d_nhwc_act_maxpool_bwd(x.data_ptr(), dp.data_ptr(), weight.data_ptr(), bias.data_ptr(), save_mean.data_ptr(),
-                                                 save_invstd.data_ptr(), N, n, H, W, float(slope), dx.data_ptr(), dw.data_ptr(),
-                                                 db.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()), "clica_bn2d_nhwc_act_maxpool_bwd")
+    fn, name = _entry("clica_bn2d_nhwc_act_maxpool_bwd", dtype)
+    check(fn(x.data_ptr(), dp.data_ptr(), weight.data_ptr(), bias.data_ptr(), save_mean.data_ptr(), save_invstd.data_ptr(), N, n, H, W,
+             float(slope), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()), name)
     return dx, dw, db
 
 

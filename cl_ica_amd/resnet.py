@@ -27,6 +27,12 @@ The channels-last stem is the unit followed by ``nn.MaxPool2d`` unless NHWC_STEM
 all "hip"): then ``bn1 + relu + maxpool`` is the fused stem unit of csrc/bn2d_nhwc.hip, which tiles the plane instead of holding it in
 LDS and, as the NCHW one, writes neither the activation nor indices.  Its default is "torch".
 
+With BF16_MODE "hip" (and NHWC_MODE "hip") the channels-last units, the fused stem (under NHWC_STEM_MODE and POOL_MODE "hip") and the
+average pool also take bf16 activations -- what ``torch.autocast("cuda", dtype=torch.bfloat16)`` makes of the convolutions' outputs -- on
+the ``_bf16`` entry points of csrc/bn2d_nhwc.hip: bf16 in and out, fp32 parameters, statistics and parameter gradients.  The pooled
+features are fp32 and ``fc`` then runs outside autocast, so everything behind the backbone is fp32.  Its default is "torch": bf16
+inputs run the modules' own forward, as they always did.  NCHW bf16 inputs do so in either mode.
+
 Both layouts share the code here: ``_layout(x)`` names the layout once per unit, and ``_unit``, ``_stem``, ``_BN2dActFn``,
 ``_BN2dActPoolFn`` and ``_GlobalAvgPoolFn`` take it as an argument that picks the ``ops`` function (``name`` or ``name_nhwc``) and the
 memory format of the incoming gradient.
@@ -66,6 +72,13 @@ NHWC_STEM_MODE = os.environ.get("CLICA_RESNET_NHWC_STEM", "torch")
 if NHWC_STEM_MODE not in ("hip", "torch"):
     raise ValueError(f"CLICA_RESNET_NHWC_STEM={NHWC_STEM_MODE!r} (one of 'hip', 'torch')")
 
+# "hip": dense channels-last bf16 inputs (autocast's) take the units and pools on the bf16 instances of csrc/bn2d_nhwc.hip where
+# NHWC_MODE -- and for the fused stem NHWC_STEM_MODE and POOL_MODE -- are "hip"; "torch": they run the modules' own forward, as before.
+# Read at call time.
+BF16_MODE = os.environ.get("CLICA_RESNET_BF16", "torch")
+if BF16_MODE not in ("hip", "torch"):
+    raise ValueError(f"CLICA_RESNET_BF16={BF16_MODE!r} (one of 'hip', 'torch')")
+
 _NHWC = torch.channels_last
 # A layout ("nchw" / "nhwc", what _layout gives) picks the memory format of a gradient and the ops function of a name, looked up on the
 # module at call time.
@@ -74,6 +87,12 @@ _FORMAT = {"nchw": torch.contiguous_format, "nhwc": _NHWC}
 
 def _op(name, layout):
     return getattr(ops, name if layout == "nchw" else name + "_nhwc")
+
+
+def _grad_like(g, out, layout):
+    """The incoming gradient in the unit's layout and in its output's element type (autograd hands a bf16 output a bf16 gradient; one
+    that arrives in fp32 is cast)."""
+    return g.to(out.dtype).contiguous(memory_format=_FORMAT[layout])
 
 
 class _BN2dActFn(torch.autograd.Function):
@@ -93,8 +112,8 @@ class _BN2dActFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gy):
         x, y, weight, save_mean, save_invstd = ctx.saved_tensors
-        dx, dr, dw, db = _op("batchnorm2d_act_bwd", ctx.layout)(x, y, gy.contiguous(memory_format=_FORMAT[ctx.layout]), weight, save_mean,
-                                                                save_invstd, ctx.slope, need_dr=ctx.needs_input_grad[1])
+        dx, dr, dw, db = _op("batchnorm2d_act_bwd", ctx.layout)(x, y, _grad_like(gy, y, ctx.layout), weight, save_mean, save_invstd, ctx.slope,
+                                                                need_dr=ctx.needs_input_grad[1])
         return dx, dr, dw, db, None, None, None
 
 
@@ -115,8 +134,8 @@ class _BN2dActPoolFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gp):
         x, weight, bias, save_mean, save_invstd = ctx.saved_tensors
-        dx, dw, db = _op("batchnorm2d_act_maxpool_bwd", ctx.layout)(x, gp.contiguous(memory_format=_FORMAT[ctx.layout]), weight, bias,
-                                                                    save_mean, save_invstd, ctx.slope)
+        dx, dw, db = _op("batchnorm2d_act_maxpool_bwd", ctx.layout)(x, _grad_like(gp, x, ctx.layout), weight, bias, save_mean, save_invstd,
+                                                                    ctx.slope)
         return dx, dw, db, None, None, None
 
 
@@ -126,18 +145,22 @@ class _GlobalAvgPoolFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, layout):
-        ctx.hw, ctx.layout = (x.shape[2], x.shape[3]), layout
+        ctx.hw, ctx.layout, ctx.dtype = (x.shape[2], x.shape[3]), layout, x.dtype
         return _op("avgpool2d_global_fwd", layout)(x)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        return _op("avgpool2d_global_bwd", ctx.layout)(gy.contiguous(), *ctx.hw), None
+        if ctx.dtype == torch.float32:
+            return _op("avgpool2d_global_bwd", ctx.layout)(gy.contiguous(), *ctx.hw), None
+        return _op("avgpool2d_global_bwd", ctx.layout)(gy.float().contiguous(), *ctx.hw, ctx.dtype), None      # (fp32 [N, C] in, bf16 out)
 
 
 def _layout(x):
     """"nchw" for a contiguous tensor (those with C = 1 or H = W = 1, the same memory in both layouts, among them), "nhwc" for any other
     dense channels-last tensor when NHWC_MODE is "hip", else None: not the kernels' input."""
+    if x.dtype == torch.bfloat16 and BF16_MODE == "hip" and NHWC_MODE == "hip" and x.numel() > 0 and x.is_contiguous(memory_format=_NHWC):
+        return "nhwc"                                       # (1 x 1 planes too: the bf16 kernels are channels-last only)
     if x.is_contiguous():
         return "nchw"
     if NHWC_MODE == "hip" and x.numel() > 0 and x.is_contiguous(memory_format=_NHWC):
@@ -149,12 +172,17 @@ def _same_layout(r, layout) -> bool:
     return r.is_contiguous() if layout == "nchw" else r.is_contiguous(memory_format=_NHWC)
 
 
+def _act_dtype_on_hip(x, layout) -> bool:
+    """fp32 in either layout; bf16 channels-last under BF16_MODE "hip" (layout "nhwc" already says NHWC_MODE "hip")."""
+    return x.dtype == torch.float32 or (x.dtype == torch.bfloat16 and BF16_MODE == "hip" and layout == "nhwc")
+
+
 def _bn2d_on_hip(m, x, layout, r=None) -> bool:
     """Do the bn2d kernels cover this module on this input of `layout` (= _layout(x)) and residual?  Anything else runs the module's own
     forward, as before."""
-    if NORM_MODE != "hip" or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or layout is None:
+    if NORM_MODE != "hip" or not x.is_cuda or not _act_dtype_on_hip(x, layout) or x.dim() != 4 or layout is None:
         return False
-    if r is not None and not (r.is_cuda and r.dtype == torch.float32 and r.shape == x.shape and _same_layout(r, layout)):
+    if r is not None and not (r.is_cuda and r.dtype == x.dtype and r.shape == x.shape and _same_layout(r, layout)):
         return False
     if not (isinstance(m, nn.BatchNorm2d) and m.affine and m.track_running_stats and m.momentum is not None and x.shape[1] == m.num_features):
         return False
@@ -216,7 +244,7 @@ def _stem(bn, relu, pool, x):
 def _avgpool_on_hip(pool, x) -> bool:
     if POOL_MODE != "hip" or NORM_MODE != "hip":
         return False
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and _layout(x) is not None and x.numel() > 0):
+    if not (x.is_cuda and x.dim() == 4 and _layout(x) is not None and _act_dtype_on_hip(x, _layout(x)) and x.numel() > 0):
         return False
     return type(pool) is nn.AdaptiveAvgPool2d and pool.output_size in (1, (1, 1)) and x.shape[2] * x.shape[3] <= ops.AVGPOOL_MAX_HW
 
@@ -272,7 +300,11 @@ class ResNet18(nn.Module):
             x = _stem(self.bn1, self.relu, self.maxpool, self.conv1(x))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         if _avgpool_on_hip(self.avgpool, x):
-            return self.fc(_GlobalAvgPoolFn.apply(x, _layout(x)))
+            feats = _GlobalAvgPoolFn.apply(x, _layout(x))
+            if x.dtype == torch.bfloat16:                 # fp32 features of the bf16 pool: the head stays fp32 inside an autocast region
+                with torch.autocast("cuda", enabled=False):
+                    return self.fc(feats)
+            return self.fc(feats)
         return self.fc(torch.flatten(self.avgpool(x), 1))
 
 

@@ -119,14 +119,30 @@ def unpack_item_list(lst):
     return [unpack_item_list(it) if isinstance(it, (tuple, list)) else it.item() for it in lst]
 
 
-def train_step(data, loss, optimizer, f, sync: bool = True):
+AMP_MODES = (None, "bf16")
+
+
+def encode(f, x, amp=None):
+    """``f(x)``; with ``amp="bf16"`` under ``torch.autocast("cuda", dtype=torch.bfloat16)``: the backbone's convolutions run in bf16 (and,
+    with resnet.BF16_MODE "hip", the units between them on the bf16 kernels), its head and everything behind it in fp32.  No loss
+    scaling: bf16 has fp32's exponent range."""
+    if amp is None:
+        return f(x)
+    if amp != "bf16":
+        raise ValueError(f"amp={amp!r} (one of {AMP_MODES})")
+    with torch.autocast("cuda", dtype=torch.bfloat16):
+        return f(x)
+
+
+def train_step(data, loss, optimizer, f, sync: bool = True, amp=None):
     """One unsupervised step (main_3dident.py:467-503): two encoder passes, ``z3_rec = roll(z1_rec)`` inside the graph,
     the loss with ``None`` latents, backward, optimizer step.  Returns ``(total, per_item, [pos_mean, neg_mean])`` as python
-    floats like the reference when ``sync`` (3 host syncs), device tensors otherwise."""
+    floats like the reference when ``sync`` (3 host syncs), device tensors otherwise.  ``amp``: see ``encode`` (the encoder passes
+    only; the loss and the optimizer stay fp32)."""
     (_z1, _z2), (x1, x2_con_x1) = data
     optimizer.zero_grad()
-    z1_rec = f(x1)
-    z2_con_z1_rec = f(x2_con_x1)
+    z1_rec = encode(f, x1, amp)
+    z2_con_z1_rec = encode(f, x2_con_x1, amp)
     del x1, x2_con_x1
     z3_rec = torch.roll(z1_rec, 1, 0)
     total_loss_value, total_loss_per_item_value, losses_value = loss(None, None, None, z1_rec, z2_con_z1_rec, z3_rec)
@@ -198,13 +214,13 @@ def make_supervised_loss(args):
     raise ValueError(f"supervised_loss {kind!r}")
 
 
-def train_step_supervised(data, loss, optimizer, f, sync: bool = True):
+def train_step_supervised(data, loss, optimizer, f, sync: bool = True, amp=None):
     """One supervised step (main_3dident.py:585-601): one encoder pass on the first view, the loss against its true latents,
     backward, optimizer step.  Returns the loss as a python float like the reference when ``sync`` (one host sync), the device
-    scalar otherwise."""
+    scalar otherwise.  ``amp``: see ``encode``."""
     (z1, _), (x1, _) = data
     optimizer.zero_grad()
-    hz1 = lazy.plain(f(x1))
+    hz1 = lazy.plain(encode(f, x1, amp))
     del x1
     total_loss_value = loss(hz1, z1.to(hz1.device))
     total_loss_value.backward()

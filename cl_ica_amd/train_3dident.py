@@ -32,7 +32,7 @@ from datetime import datetime
 import numpy as np
 import torch
 
-from . import disentanglement_utils, invertible_network_utils, latent_spaces, lazy, optim, spaces, threedident
+from . import disentanglement_utils, invertible_network_utils, latent_spaces, lazy, optim, resnet, spaces, threedident
 from .datasets import BatchLoader, SequentialThreeDIdentDataset, ThreeDIdentDataset
 
 __all__ = ["parse_args", "setup_latent_space", "latent_dimensions_to_use", "evaluate", "train_unsupervised", "train_supervised", "test",
@@ -82,18 +82,38 @@ _EXTRA_ARGS = [
     ("--seed", dict(type=int, default=None, help="Seeds numpy, random, torch and the device samplers.")),
     ("--image-cache", dict(type=str, default=None,
                            help=".npy file the decoded image folder is written to once and memory-mapped from afterwards.")),
+    ("--amp", dict(default="off", choices=("off", "bf16"),
+                   help="bf16: the backbone in bf16 mixed precision (autocast convolutions, channels-last bf16 HIP units between them); "
+                        "head, loss, optimizer and model files stay fp32.")),
 ]
+# The flags of _EXTRA_ARGS that say HOW the run computes, not what it computes.  They are taken off the command line ahead of the
+# table's parser: build_parser() stays the reference's surface plus --seed and --image-cache, the set tests/test_train_3dident_host.py
+# pins.
+_RUN_ARGS = ("--amp",)
 
 
 def build_parser() -> argparse.ArgumentParser:
-    ap = argparse.ArgumentParser(description="Disentanglement with InfoNCE/Contrastive Learning - 3DIdent (MI355X)")
+    run = "; ".join(f"{flag} {{{','.join(kw['choices'])}}} (default {kw['default']}): {kw['help']}" for flag, kw in _EXTRA_ARGS
+                    if flag in _RUN_ARGS)
+    ap = argparse.ArgumentParser(description="Disentanglement with InfoNCE/Contrastive Learning - 3DIdent (MI355X)",
+                                 epilog="Read ahead of the options above, how the run computes: " + run)
     for flag, kw in _ARGS + _EXTRA_ARGS:
-        ap.add_argument(flag, **kw)
+        if flag not in _RUN_ARGS:
+            ap.add_argument(flag, **kw)
+    return ap
+
+
+def _run_parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False, usage=argparse.SUPPRESS)
+    for flag, kw in _EXTRA_ARGS:
+        if flag in _RUN_ARGS:
+            ap.add_argument(flag, **kw)
     return ap
 
 
 def parse_args(argv=None):
-    args = build_parser().parse_args(argv)
+    run, rest = _run_parser().parse_known_args(argv)
+    args = build_parser().parse_args(rest, namespace=run)
     if args.no_spotlight:                                                   # :108-111
         args.no_spotlight_color = True
         args.no_spotlight_position = True
@@ -110,7 +130,23 @@ def parse_args(argv=None):
         raise AssertionError("only one of --box-constraint / --sphere-constraint")
     if args.save_model is not None and not os.path.exists(os.path.dirname(args.save_model)):
         raise AssertionError(f"Directory {os.path.dirname(args.save_model)} to save model does not exist")
+    if args.amp != "off" and (args.dummy_mixing or args.identity_solution or args.identity_mixing_and_solution):
+        raise AssertionError(f"--amp {args.amp} is the backbone's mixed precision: --dummy-mixing / --identity-solution / "
+                             "--identity-mixing-and-solution have no backbone")
     return args
+
+
+def _amp(args):
+    """What the steps and the evaluation take as ``amp``: None for ``--amp off`` (and for argument objects from before the flag)."""
+    amp = getattr(args, "amp", "off")
+    return None if amp == "off" else amp
+
+
+def _amp_batch(x, amp):
+    """The image batch as the mixed-precision backbone takes it: dense channels-last.  ``amp`` None: x itself."""
+    if amp is None or x is None:
+        return x
+    return x.contiguous(memory_format=torch.channels_last)
 
 
 # ------------------------------------------------------------------------------------------------------------------ latent space
@@ -237,9 +273,10 @@ def _infinite(loader):
 
 
 # ------------------------------------------------------------------------------------------------------------------ evaluation
-def evaluate(args, f, test_iterator, evaluate_permutation_disentanglement, no_pairs=False, g=None):
+def evaluate(args, f, test_iterator, evaluate_permutation_disentanglement, no_pairs=False, g=None, amp=None):
     """``(MCC, linear R2, mse, linear_fit_mse)`` over ``n_eval_samples // batch_size`` batches (main_3dident.py:656-748): the scores on
-    device tensors, the two per-dimension errors as NumPy vectors, ``np.inf`` where the reference returns it."""
+    device tensors, the two per-dimension errors as NumPy vectors, ``np.inf`` where the reference returns it.  ``amp``: the encoder
+    passes as ``threedident.encode`` runs them."""
     zs, hzs = [], []
     with torch.no_grad():
         for _ in range(args.n_eval_samples // args.batch_size):
@@ -253,7 +290,7 @@ def evaluate(args, f, test_iterator, evaluate_permutation_disentanglement, no_pa
             if args.identity_mixing_and_solution:
                 batch_hz = batch_z
             else:
-                batch_hz = lazy.plain(f(batch_x)).detach()
+                batch_hz = lazy.plain(threedident.encode(f, _amp_batch(batch_x, amp), amp)).detach()
             zs.append(batch_z)
             hzs.append(batch_hz)
     if not zs:
@@ -273,7 +310,7 @@ def evaluate(args, f, test_iterator, evaluate_permutation_disentanglement, no_pa
 
 
 def test(args, test_loader, f, g=None):
-    scores = evaluate(args, f, _infinite(test_loader), not args.identity_solution, True, g=g)
+    scores = evaluate(args, f, _infinite(test_loader), not args.identity_solution, True, g=g, amp=_amp(args))
     permutation_score, linear_score, mse, linear_fit_mse = scores
     print(f"Lin. Disentanglement: {linear_score}, MCC: {permutation_score}, MSE: {mse}, lin. fit MSE: {linear_fit_mse}")
     return scores
@@ -308,6 +345,7 @@ def _fetch(pending, total_loss_values):
 def train_unsupervised(args, train_loader, f, n_non_angular_latents, g=None):
     """main_3dident.py:402-566.  Returns ``dict(losses, optimizer, scores)``."""
     n_log_steps, n_steps = args.n_log_steps, args.iterations
+    amp = _amp(args)
     loss = _three_values(threedident.make_unsupervised_loss(args, n_non_angular_latents))
     optimizer = _make_optimizer(args, f)
     total_loss_values, pending = [], []
@@ -326,12 +364,14 @@ def train_unsupervised(args, train_loader, f, n_non_angular_latents, g=None):
             z1_rec = z1 * identity_scale
             total, per_item, _parts = loss(None, None, None, z1_rec, z2_con_z1 * identity_scale, torch.roll(z1_rec, 1, 0))
         else:
-            total, per_item, _parts = threedident.train_step(data, loss, optimizer, f, sync=False)
+            if amp is not None:
+                data = ((z1, z2_con_z1), (_amp_batch(data[1][0], amp), _amp_batch(data[1][1], amp)))
+            total, per_item, _parts = threedident.train_step(data, loss, optimizer, f, sync=False, amp=amp)
         pending.append(total)
         del data, x1, x2_con_x1
         log = is_log_step(global_step, n_log_steps, n_steps)
         if log:
-            scores = evaluate(args, f, train_iterator, True, g=g)
+            scores = evaluate(args, f, train_iterator, True, g=g, amp=amp)
             permutation_score, linear_score, mse, linear_fit_mse = scores
         else:
             linear_score = permutation_score = np.inf
@@ -364,6 +404,7 @@ def train_unsupervised(args, train_loader, f, n_non_angular_latents, g=None):
 def train_supervised(args, train_loader, f, g=None):
     """main_3dident.py:569-653 (the evaluation comes BEFORE the step here).  Returns ``dict(losses, optimizer, scores)``."""
     n_log_steps, n_steps = args.n_log_steps, args.iterations
+    amp = _amp(args)
     loss = threedident.make_supervised_loss(args)
     optimizer = None if args.identity_solution else _make_optimizer(args, f)
     total_loss_values, pending = [], []
@@ -374,7 +415,7 @@ def train_supervised(args, train_loader, f, g=None):
     for global_step in range(n_steps):
         log = is_log_step(global_step, n_log_steps, n_steps)
         if log:
-            scores = evaluate(args, f, train_iterator, False, g=g)
+            scores = evaluate(args, f, train_iterator, False, g=g, amp=amp)
             permutation_score, linear_score, mse, linear_fit_mse = scores
         else:
             linear_score = permutation_score = np.inf
@@ -386,7 +427,9 @@ def train_supervised(args, train_loader, f, g=None):
                 (z1, z2), _x = data
                 with torch.no_grad():
                     data = ((z1, z2), (g(z1), None))
-            pending.append(threedident.train_step_supervised(data, loss, optimizer, f, sync=False))
+            if amp is not None:
+                data = (data[0], (_amp_batch(data[1][0], amp), data[1][1]))
+            pending.append(threedident.train_step_supervised(data, loss, optimizer, f, sync=False, amp=amp))
         else:
             _fetch(pending, total_loss_values)
             total_loss_values.append(np.inf)
@@ -441,7 +484,24 @@ def main(argv=None, *, images=None, base_encoder=None):
         f.load_state_dict(strip_module_prefix(torch.load(args.load_model, map_location="cpu", weights_only=True)))
         print("Model loaded:", args.load_model)
     f = f.to(device)
+    if _amp(args) is not None:
+        # parameters stay fp32 (the model file does not change); the kernels between the convolutions take over the bf16 activations
+        f = f.to(memory_format=torch.channels_last)
+        print(f"Mixed precision: --amp {args.amp}: channels-last model and batches, convolutions under torch.autocast(bfloat16), "
+              "resnet NHWC_MODE = NHWC_STEM_MODE = BF16_MODE = 'hip'; head, loss and optimizer in fp32")
+        switches = {name: getattr(resnet, name) for name in ("NHWC_MODE", "NHWC_STEM_MODE", "BF16_MODE")}
+        for name in switches:
+            setattr(resnet, name, "hip")
+        try:
+            return _run(args, f, device, latent_space, n_non_angular_latents, n_angular_latents, images)
+        finally:                                      # (the caller's switches are the caller's)
+            for name, value in switches.items():
+                setattr(resnet, name, value)
+    return _run(args, f, device, latent_space, n_non_angular_latents, n_angular_latents, images)
 
+
+def _run(args, f, device, latent_space, n_non_angular_latents, n_angular_latents, images):
+    """The mode's loop on the model as ``main`` set it up, and the final save."""
     g = None
     if args.dummy_mixing:
         g = invertible_network_utils.construct_invertible_mlp(n_angular_latents + n_non_angular_latents, n_layers=3, act_fct="leaky_relu",

@@ -809,6 +809,42 @@ int clica_bn2d_nhwc_act_maxpool_bwd(const float* X, const float* dP, const float
 int clica_avgpool2d_global_nhwc_fwd(const float* X, int64_t N, int32_t HW, int32_t C, float* Y, clica_stream_t stream);
 int clica_avgpool2d_global_nhwc_bwd(const float* dY, int64_t N, int32_t HW, int32_t C, float* dX, clica_stream_t stream);
 
+/* The channels-last entry points above on bf16 ACTIVATIONS, carried as their 16 bits: X, R, Y, dY, dX, dR of the unit, X, P, dP, dX of
+ * the stem unit, X and dX of the average pool.  Everything else stays fp32: gamma, beta, save_mean, save_invstd, the running statistics,
+ * dgamma, dbeta, the workspace partials, LDS, every accumulation, and the average pool's Y[N, C] and dY[N, C].  Argument lists,
+ * workspace-size functions (clica_bn2d_nhwc_workspace_bytes, clica_bn2d_nhwc_maxpool_workspace_bytes), checks and return codes are those
+ * of the fp32 entry point of the same name.
+ * A value is widened on load by the 16-bit shift (exact), the kernel computes in fp32 what the fp32 entry point computes, and an output
+ * is rounded once at the store, to nearest with ties to even as Tensor.to(torch.bfloat16) rounds (a NaN becomes 0x7fc0).  The geometry
+ * is the fp32 one, from the shape alone: a lane owns the same 4 consecutive channels when C % 4 == 0 (one 8-byte access when every
+ * activation pointer is 8-byte aligned, else 2-byte accesses of the same values in the same order), otherwise 1; the same splits, merge
+ * order, tiles and workspace bytes.  Hence: every fp32 output has the bits the fp32 entry point gives on the upcast activations, and
+ * every bf16 output is that entry point's output rounded to bf16 -- the stem's first maximum is taken among the fp32 activations and
+ * rounded afterwards. */
+int clica_bn2d_nhwc_act_fwd_train_bf16(const uint16_t* X, const uint16_t* R /*or NULL*/, const float* gamma, const float* beta, int64_t M,
+                                       int32_t C, float eps, float momentum, float slope, uint16_t* Y, float* save_mean, float* save_invstd,
+                                       float* running_mean /*[C] or NULL*/, float* running_var /*[C] or NULL*/, void* workspace,
+                                       size_t workspace_bytes, clica_stream_t stream);
+int clica_bn2d_nhwc_act_fwd_eval_bf16(const uint16_t* X, const uint16_t* R /*or NULL*/, const float* gamma, const float* beta,
+                                      const float* running_mean, const float* running_var, int64_t M, int32_t C, float eps, float slope,
+                                      uint16_t* Y, clica_stream_t stream);
+int clica_bn2d_nhwc_act_bwd_bf16(const uint16_t* X, const uint16_t* Y, const uint16_t* dY, const float* gamma, const float* save_mean,
+                                 const float* save_invstd, int64_t M, int32_t C, float slope, uint16_t* dX, uint16_t* dR /*or NULL*/,
+                                 float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, clica_stream_t stream);
+int clica_bn2d_nhwc_act_maxpool_fwd_train_bf16(const uint16_t* X, const float* gamma, const float* beta, int64_t N, int32_t C, int32_t H,
+                                               int32_t W, float eps, float momentum, float slope, uint16_t* P, float* save_mean,
+                                               float* save_invstd, float* running_mean /*[C] or NULL*/, float* running_var /*[C] or NULL*/,
+                                               void* workspace, size_t workspace_bytes, clica_stream_t stream);
+int clica_bn2d_nhwc_act_maxpool_fwd_eval_bf16(const uint16_t* X, const float* gamma, const float* beta, const float* running_mean,
+                                              const float* running_var, int64_t N, int32_t C, int32_t H, int32_t W, float eps, float slope,
+                                              uint16_t* P, clica_stream_t stream);
+int clica_bn2d_nhwc_act_maxpool_bwd_bf16(const uint16_t* X, const uint16_t* dP, const float* gamma, const float* beta,
+                                         const float* save_mean, const float* save_invstd, int64_t N, int32_t C, int32_t H, int32_t W,
+                                         float slope, uint16_t* dX, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
+                                         clica_stream_t stream);
+int clica_avgpool2d_global_nhwc_fwd_bf16(const uint16_t* X, int64_t N, int32_t HW, int32_t C, float* Y, clica_stream_t stream);
+int clica_avgpool2d_global_nhwc_bwd_bf16(const float* dY, int64_t N, int32_t HW, int32_t C, uint16_t* dX, clica_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Convolution stack of the KITTI-masks encoder  --  BetaVAE_H, /root/reference/kitti_masks/model.py:41-56:
  * Conv2d(k = 4, stride 2, pad 1) + ReLU stages as implicit GEMMs (fp32 MFMA, csrc/linear.hip, conv section), channels-last.

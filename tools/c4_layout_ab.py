@@ -5,6 +5,8 @@
     (b) nhwc-torch  channels_last model and inputs, CLICA_RESNET_NHWC=torch: torch's / MIOpen's own BatchNorm, ReLU, add
     (c) nhwc-hip    channels_last model and inputs, CLICA_RESNET_NHWC=hip: the units of csrc/bn2d_nhwc.hip
     (d) nhwc-hip-stem  as (c) with CLICA_RESNET_NHWC_STEM=hip: the stem's bn1 + relu + maxpool as the fused unit of csrc/bn2d_nhwc.hip
+    (e) nhwc-torch-bf16     as (b) with the encoder passes under torch.autocast(bfloat16): what bf16 mixed precision was before BF16_MODE
+    (f) nhwc-hip-stem-bf16  as (d) under the same autocast with CLICA_RESNET_BF16=hip: the bf16 instances of csrc/bn2d_nhwc.hip
 
   python tools/c4_layout_ab.py                      a throw-away run of every leg (MIOpen's find step), then two rounds alternating the
                                                     legs; each figure the median of three 20-step windows after 6 warm-up steps
@@ -12,7 +14,8 @@
   python tools/c4_layout_ab.py --leg nhwc-hip       one leg alone, 6 + 30 steps: the program for `rocprofv3 --kernel-trace --stats -- ...`
   python tools/c4_layout_ab.py --units              the fused unit alone per ResNet-18 (M, C) at N = 1024, NHWC against NCHW, event-timed
                                                     calls (forward = statistics + apply, backward = sums + backward apply) and TB/s;
-                                                    then the stem with its max-pool, fused, in both layouts
+                                                    then the stem with its max-pool, fused, in both layouts; then the channels-last
+                                                    units, stem and average pool on bf16 activations (layout "nhwc-bf16")
   python tools/c4_layout_ab.py --summarise T.csv    buckets and per-(kernel, grid) rows of a rocprofv3 *_kernel_trace.csv (no GPU)
 Every mode prints JSON lines; --out FILE also appends them there."""
 import argparse
@@ -27,7 +30,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 # leg -> (memory format, NHWC_MODE, NHWC_STEM_MODE)
 LEGS = {"nchw": ("contiguous", "torch", "torch"), "nhwc-torch": ("channels_last", "torch", "torch"),
-        "nhwc-hip": ("channels_last", "hip", "torch"), "nhwc-hip-stem": ("channels_last", "hip", "hip")}
+        "nhwc-hip": ("channels_last", "hip", "torch"), "nhwc-hip-stem": ("channels_last", "hip", "hip"),
+        "nhwc-torch-bf16": ("channels_last", "torch", "torch"), "nhwc-hip-stem-bf16": ("channels_last", "hip", "hip")}
+# leg -> (BF16_MODE, train_step's amp); every other leg: ("torch", None)
+BF16_LEGS = {"nhwc-torch-bf16": ("torch", "bf16"), "nhwc-hip-stem-bf16": ("hip", "bf16")}
 # ResNet-18's units at N = 1024 on 64 x 64 images: (name, N, C, H, W, units with / without a residual per view)
 UNIT_SHAPES = [("stem", 1024, 64, 32, 32), ("layer 1", 1024, 64, 16, 16), ("layer 2", 1024, 128, 8, 8), ("layer 3", 1024, 256, 4, 4),
                ("layer 4", 1024, 512, 2, 2)]
@@ -47,6 +53,7 @@ def make_leg(leg):
     from cl_ica_amd import resnet, threedident as T
     from cl_ica_amd.optim import Adam
     fmt_name, nhwc_mode, stem_mode = LEGS[leg]
+    bf16_mode, amp = BF16_LEGS.get(leg, ("torch", None))
     fmt = getattr(torch, fmt_name + "_format" if fmt_name == "contiguous" else fmt_name)
     dev = torch.device("cuda")
     torch.manual_seed(0)
@@ -55,6 +62,9 @@ def make_leg(leg):
                               unsupervised_loss="l2", identity_solution=False, encoder="rn18")
     f = T.setup_f(a, 3, 0).to(dev).to(memory_format=fmt)
     f.train()
+    if amp is not None and bf16_mode == "torch":
+        # torch's modules hand the head bf16 logits, which the HIP head (fp32 only) refuses: this leg widens them behind the backbone
+        f[0].register_forward_hook(lambda mod, inp, out: out.float())
     loss = T.make_unsupervised_loss(a, 3)
     opt = Adam(f.parameters(), lr=1e-4)
     x1 = torch.randn(1024, 3, 64, 64, device=dev)
@@ -62,16 +72,20 @@ def make_leg(leg):
     x1 = x1.contiguous(memory_format=fmt)
 
     def step():
-        resnet.NHWC_MODE, resnet.NHWC_STEM_MODE = nhwc_mode, stem_mode            # (read at call time)
-        return T.train_step(((None, None), (x1, x2)), loss, opt, f, sync=False)[0]
+        resnet.NHWC_MODE, resnet.NHWC_STEM_MODE, resnet.BF16_MODE = nhwc_mode, stem_mode, bf16_mode      # (read at call time)
+        if amp is None:
+            return T.train_step(((None, None), (x1, x2)), loss, opt, f, sync=False)[0]
+        return T.train_step(((None, None), (x1, x2)), loss, opt, f, sync=False, amp=amp)[0]
     return step
 
 
 def run_leg(leg, steps, warmup, windows):
     import torch
     step = make_leg(leg)
+    first = None
     for _ in range(warmup):
         last = step()
+        first = last if first is None else first
     torch.cuda.synchronize()
     ws = []
     for _ in range(windows):
@@ -85,6 +99,8 @@ def run_leg(leg, steps, warmup, windows):
     el = statistics.median(ws)
     res = {"leg": leg, "steps_per_s": round(steps / el, 2), "ms_per_step": round(1e3 * el / steps, 2), "final_loss": round(float(last.item()), 5),
            "windows_s": [round(w, 4) for w in ws]}
+    if leg in BF16_LEGS and first is not None:
+        res["first_loss"] = round(float(first.item()), 5)
     del step
     torch.cuda.empty_cache()
     return res
@@ -165,6 +181,75 @@ def stem_units(out, reps=20):
         torch.cuda.empty_cache()
 
 
+def _timed(call, reps):
+    import torch
+    for _ in range(3):
+        call()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        call()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / reps
+
+
+def bf16_units(out, reps=20):
+    """The channels-last units, the fused stem and the average pool on bf16 activations, at the shapes and with the calls of units()
+    and stem_units(): E is now N C H W x 2 bytes, the byte counts are the same multiples of it (the average pool: E in, E out)."""
+    import torch
+    from cl_ica_amd import ops
+    dev, bf = torch.device("cuda"), torch.bfloat16
+    nhwc = lambda t: t.contiguous(memory_format=torch.channels_last)
+    for name, N, C, H, W in UNIT_SHAPES:
+        E = N * C * H * W * 2
+        w = torch.ones(C, device=dev); b = torch.zeros(C, device=dev)
+        x, r, dy = (nhwc(torch.randn(N, C, H, W, device=dev).to(bf)) for _ in range(3))
+        fwd, bwd, ev = ops.batchnorm2d_act_fwd_nhwc, ops.batchnorm2d_act_bwd_nhwc, ops.batchnorm2d_act_eval_nhwc
+        for res in (False, True):
+            rr = r if res else None
+            y, m, i = fwd(x, w, b, None, None, 1e-5, 0.1, 0.0, residual=rr)
+            calls = {"forward (statistics + apply)": (lambda: fwd(x, w, b, None, None, 1e-5, 0.1, 0.0, residual=rr), (4 if res else 3) * E),
+                     "backward (sums + backward apply)": (lambda: bwd(x, y, dy, w, m, i, 0.0, need_dr=res), (8 if res else 7) * E),
+                     "inference apply": (lambda: ev(x, w, b, m, i.reciprocal().square(), 1e-5, 0.0, residual=rr), (3 if res else 2) * E)}
+            for what, (call, nbytes) in calls.items():
+                us = _timed(call, reps)
+                emit(out, {"unit": name, "M": N * H * W, "C": C, "E_MB": round(E / 1e6, 1), "layout": "nhwc-bf16", "residual": res,
+                           "call": what, "us_per_call": round(us, 1), "TB_per_s": round(nbytes / us / 1e6, 2)})
+        del x, r, dy, y
+        torch.cuda.empty_cache()
+    name, N, C, H, W = UNIT_SHAPES[0]
+    E = N * C * H * W * 2
+    w = torch.ones(C, device=dev); b = torch.zeros(C, device=dev)
+    x = nhwc(torch.randn(N, C, H, W, device=dev).to(bf))
+    fwd, bwd, ev = ops.batchnorm2d_act_maxpool_fwd_nhwc, ops.batchnorm2d_act_maxpool_bwd_nhwc, ops.batchnorm2d_act_maxpool_eval_nhwc
+    p, m, i = fwd(x, w, b, None, None, 1e-5, 0.1, 0.0)
+    dp = nhwc(torch.randn(*p.shape, device=dev).to(bf))
+    calls = {"forward (statistics + pool)": (lambda: fwd(x, w, b, None, None, 1e-5, 0.1, 0.0), 2.25 * E),
+             "backward (sums + backward apply)": (lambda: bwd(x, dp, w, b, m, i, 0.0), 3.5 * E),
+             "inference pool": (lambda: ev(x, w, b, m, i.reciprocal().square(), 1e-5, 0.0), 1.25 * E)}
+    for what, (call, nbytes) in calls.items():
+        us = _timed(call, reps)
+        emit(out, {"unit": "stem + max-pool", "M": N * H * W, "C": C, "E_MB": round(E / 1e6, 1), "layout": "nhwc-bf16", "call": what,
+                   "us_per_call": round(us, 1), "TB_per_s": round(nbytes / us / 1e6, 2)})
+    del x, p, dp
+    torch.cuda.empty_cache()
+    name, N, C, H, W = UNIT_SHAPES[-1]                        # the average pool sits behind layer 4
+    for dtype, tag in ((torch.float32, "nhwc"), (bf, "nhwc-bf16")):
+        x = nhwc(torch.randn(N, C, H, W, device=dev).to(dtype))
+        E = x.numel() * x.element_size()
+        g = torch.randn(N, C, device=dev)
+        calls = {"average pool forward": (lambda: ops.avgpool2d_global_fwd_nhwc(x), E + N * C * 4),
+                 "average pool backward": (lambda: ops.avgpool2d_global_bwd_nhwc(g, H, W, dtype), E + N * C * 4)}
+        for what, (call, nbytes) in calls.items():
+            us = _timed(call, reps)
+            emit(out, {"unit": "average pool", "M": N * H * W, "C": C, "E_MB": round(E / 1e6, 1), "layout": tag, "call": what,
+                       "us_per_call": round(us, 1), "TB_per_s": round(nbytes / us / 1e6, 2)})
+        del x
+    torch.cuda.empty_cache()
+
+
 def bucket_of(name):
     n = name
     if "clica::bn2d::nhwc::avgpool" in n or "clica::bn2d::nhwc::pool_" in n or "clica::avgpool" in n or "clica::bn2d::pool_" in n:
@@ -236,7 +321,8 @@ def main():
         raise SystemExit("c4_layout_ab.py measures on the GPU: none here")
     if args.units:
         units(args.out)
-        return stem_units(args.out)
+        stem_units(args.out)
+        return bf16_units(args.out)
     if args.leg:
         return emit(args.out, dict(run_leg(args.leg, args.steps or 30, args.warmup, 1), run="alone"))
     legs = args.legs.split(",") if args.legs else list(LEGS)
