@@ -281,6 +281,8 @@ SIGNATURES: Dict[str, list] = {
     "clica_kitti_sample_pairs": [C.c_void_p, c_i64, c_i64, c_f32p, c_i32, C.c_void_p, C.c_void_p, C.c_void_p, c_i64, c_i64, C.c_void_p, c_i64,
                                  c_i32, C.c_uint64, C.c_void_p, c_f32p, c_f32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "clica_image_gather_norm": [C.c_void_p, c_i64, c_i32, c_i32, c_i32, C.c_void_p, c_i64, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p],
+    "clica_image_gather_norm_ex": [C.c_void_p, c_i64, c_i32, c_i32, c_i32, C.c_void_p, c_i64, C.c_void_p, C.c_void_p, C.c_void_p, c_i32, c_i32,
+                                   C.c_void_p],
     "clica_image_channel_stats": [C.c_void_p, c_i64, c_i32, c_i32, c_i32, C.c_void_p, C.c_void_p],
     "clica_moments_workspace_bytes": [c_i64, c_i32, C.POINTER(c_size)],
     "clica_moments": [c_f32p, c_i64, c_i32, c_f32p, c_i64, c_i32, c_i64, C.c_void_p, C.c_void_p, c_size, C.c_void_p],

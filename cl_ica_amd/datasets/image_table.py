@@ -158,10 +158,13 @@ class ImageTable:
         return cls(cls.decode_folder(paths, cache), device=device)
 
     # ------------------------------------------------------------------ the device side
-    def gather(self, index, normalize=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """float32 ``(len(index), C, H, W)``: ToTensor of the rows `index`, then Normalize with ``normalize = (mean, std)`` if given."""
+    def gather(self, index, normalize=None, out: Optional[torch.Tensor] = None, *, memory_format=torch.contiguous_format,
+               dtype=torch.float32) -> torch.Tensor:
+        """``(len(index), C, H, W)``: ToTensor of the rows `index`, then Normalize with ``normalize = (mean, std)`` if given.  float32 NCHW
+        by default; `memory_format` ``torch.channels_last`` / `dtype` ``torch.bfloat16`` write the batch as a channels-last / mixed-precision
+        backbone takes it (``ops.image_gather_norm``).  `out` must match shape, layout, dtype and device (``ValueError``)."""
         mean, std = (None, None) if normalize is None else normalize
-        return ops.image_gather_norm(self.table, index, mean, std, out=out)
+        return ops.image_gather_norm(self.table, index, mean, std, out=out, memory_format=memory_format, dtype=dtype)
 
     def channel_sums(self) -> torch.Tensor:
         return ops.image_channel_sums(self.table)

@@ -155,11 +155,16 @@ class ThreeDIdentDataset:
         normalize: ``(mean, std)`` per channel, applied on the device after ``/ 255``; ``None``: ToTensor alone.
         dummy_images: images are ``torch.ones(B, 1)`` and no file is read (the reference's ``loader=lambda _: torch.ones(1)``).
         cache: ``.npy`` file the decoded folder is written to once and memory-mapped from afterwards.
+        image_format, image_dtype: layout (``torch.contiguous_format`` | ``torch.channels_last``) and element type (``torch.float32`` |
+            ``torch.bfloat16``) of the image batches (``ImageTable.gather``); the defaults are float32 NCHW.
     """
 
     def __init__(self, root, latent_space, transform=None, approximate_mode=False, use_gpu=False, loader=None,
-                 latent_dimensions_to_use=None, *, images=None, normalize=None, dummy_images=False, device="cuda", cache=None):
+                 latent_dimensions_to_use=None, *, images=None, normalize=None, dummy_images=False, device="cuda", cache=None,
+                 image_format=torch.contiguous_format, image_dtype=torch.float32):
         _no_host_hooks("ThreeDIdentDataset", transform, loader)
+        ops.image_format_args(image_format, image_dtype)
+        self.image_format, self.image_dtype = image_format, image_dtype
         if approximate_mode:
             raise NotImplementedError("ThreeDIdentDataset(approximate_mode=True): faiss's IVF / HNSW index is not built; the exact search "
                                       "over the table in HBM is one kernel (clica_nn_search)")
@@ -185,14 +190,16 @@ class ThreeDIdentDataset:
     def __repr__(self) -> str:
         return f"Dataset {self.__class__.__name__}\n    Number of datapoints: {len(self.pairs)}\n    Root location: {self.root}"
 
-    def batch(self, batch_size: int):
+    def batch(self, batch_size: int, *, image_format=None, image_dtype=None):
         """``((z, z~), (x, x~))`` for `batch_size` freshly sampled pairs, everything on the device: latents float32 (B, d), images
-        float32 (B, C, H, W) -- the two halves of ONE gather's output."""
+        (B, C, H, W) in the dataset's (or the given) layout and element type -- the two halves of ONE gather's output."""
+        image_format = self.image_format if image_format is None else image_format
+        image_dtype = self.image_dtype if image_dtype is None else image_dtype
         index_z, index_zt, z, zt = self.pairs.sample(int(batch_size))
         if self.dummy_images:
             ones = torch.ones((2 * int(batch_size), 1), dtype=torch.float32, device=self.device)
             return (z, zt), (ones[:batch_size], ones[batch_size:])
-        x = self.images.gather(torch.cat([index_z, index_zt]), self.normalize)
+        x = self.images.gather(torch.cat([index_z, index_zt]), self.normalize, memory_format=image_format, dtype=image_dtype)
         return (z, zt), (x[:batch_size], x[batch_size:])
 
     def __getitem__(self, item):
@@ -206,8 +213,10 @@ class SequentialThreeDIdentDataset:
     ``ThreeDIdentDataset``'s."""
 
     def __init__(self, root, transform=None, loader=None, latent_dimensions_to_use=None, *, images=None, normalize=None, device="cuda",
-                 cache=None):
+                 cache=None, image_format=torch.contiguous_format, image_dtype=torch.float32):
         _no_host_hooks("SequentialThreeDIdentDataset", transform, loader)
+        ops.image_format_args(image_format, image_dtype)
+        self.image_format, self.image_dtype = image_format, image_dtype
         self.root = root
         self.device = torch.device(device)
         latents, self.unfiltered_latents = _load_latents(root, latent_dimensions_to_use)
@@ -228,7 +237,7 @@ class SequentialThreeDIdentDataset:
         if index.numel() and (int(index.min()) < -n or int(index.max()) >= n):
             raise IndexError(f"index out of range for {n} samples")
         index = torch.where(index < 0, index + n, index)
-        return self.latents[index], self.images.gather(index, self.normalize)
+        return self.latents[index], self.images.gather(index, self.normalize, memory_format=self.image_format, dtype=self.image_dtype)
 
     def __getitem__(self, item):
         z, x = self.batch([int(item)])
@@ -241,12 +250,17 @@ class BatchLoader:
     Over ``ThreeDIdentDataset`` (length ``sys.maxsize``, every item a fresh draw): an endless iterator of ``dataset.batch(batch_size)``.
     Over ``SequentialThreeDIdentDataset``: one epoch per ``iter()``, every index exactly once -- in order, or with ``shuffle`` in a fresh
     device permutation each epoch from a device generator seeded with `seed` -- and the ragged last batch is kept (``drop_last=False``).
-    The epoch's index batches never visit the host.
+    The epoch's index batches never visit the host.  `image_format` / `image_dtype`: layout and element type of the image batches
+    (``ImageTable.gather``); ``None``, the default: the dataset's own.
     """
 
-    def __init__(self, dataset, batch_size: int, shuffle: bool = False, seed: Optional[int] = None):
+    def __init__(self, dataset, batch_size: int, shuffle: bool = False, seed: Optional[int] = None, *, image_format=None,
+                 image_dtype=None):
         if int(batch_size) < 1:
             raise ValueError(f"batch_size={batch_size}")
+        self.image_format = image_format if image_format is not None else getattr(dataset, "image_format", torch.contiguous_format)
+        self.image_dtype = image_dtype if image_dtype is not None else getattr(dataset, "image_dtype", torch.float32)
+        ops.image_format_args(self.image_format, self.image_dtype)
         self.dataset, self.batch_size, self.shuffle = dataset, int(batch_size), bool(shuffle)
         self.endless = isinstance(dataset, ThreeDIdentDataset)
         self.generator = None
@@ -262,9 +276,9 @@ class BatchLoader:
     def __iter__(self):
         if self.endless:
             while True:
-                yield self.dataset.batch(self.batch_size)
+                yield self.dataset.batch(self.batch_size, image_format=self.image_format, image_dtype=self.image_dtype)
         ds, n = self.dataset, len(self.dataset)
         order = torch.randperm(n, device=ds.device, generator=self.generator) if self.shuffle else torch.arange(n, device=ds.device)
         for b in range(len(self)):
             index = order[b * self.batch_size:(b + 1) * self.batch_size]
-            yield ds.latents[index], ds.images.gather(index, ds.normalize)
+            yield ds.latents[index], ds.images.gather(index, ds.normalize, memory_format=self.image_format, dtype=self.image_dtype)

@@ -1572,12 +1572,32 @@ def _host_floats(name: str, v, n: int):
     return (C.c_float * n)(*[float(e) for e in v])
 
 
-def image_gather_norm(table: torch.Tensor, index: torch.Tensor, mean=None, std=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """float32 batch [len(index), C, H, W] of the rows `index` of a uint8 image table [N, H, W, C] in HBM, one launch
-    (clica_image_gather_norm): ``((v / 255) - mean[c]) / std[c]``, torchvision's ToTensor + Normalize (main_3dident.py:787-796) as three
-    correctly rounded fp32 operations; ``mean is std is None``: ToTensor alone.  `mean` / `std` are host sequences of C numbers, read at
-    the call.  `out`: a float32 buffer of that shape to write into (a captured graph keeps its buffer; `index` is then read on replay)."""
+IMAGE_LAYOUTS = {torch.contiguous_format: 0, torch.channels_last: 1}      # enum clica_image_layout
+IMAGE_DTYPES = {torch.float32: 0, torch.bfloat16: 1}                      # enum clica_image_dtype
+
+
+def image_format_args(memory_format=torch.contiguous_format, dtype=torch.float32) -> Tuple[int, int]:
+    """(layout, dtype) codes of clica_image_gather_norm_ex for an image batch's `memory_format` / `dtype`, or ``ValueError``."""
+    if memory_format not in IMAGE_LAYOUTS:
+        raise ValueError(f"memory_format={memory_format!r} (torch.contiguous_format or torch.channels_last)")
+    if dtype not in IMAGE_DTYPES:
+        raise ValueError(f"dtype={dtype!r} (torch.float32 or torch.bfloat16)")
+    return IMAGE_LAYOUTS[memory_format], IMAGE_DTYPES[dtype]
+
+
+def image_gather_norm(table: torch.Tensor, index: torch.Tensor, mean=None, std=None, out: Optional[torch.Tensor] = None, *,
+                      memory_format=torch.contiguous_format, dtype=torch.float32) -> torch.Tensor:
+    """Batch of logical shape [len(index), C, H, W] of the rows `index` of a uint8 image table [N, H, W, C] in HBM, one launch
+    (clica_image_gather_norm / _ex): ``((v / 255) - mean[c]) / std[c]``, torchvision's ToTensor + Normalize (main_3dident.py:787-796) as
+    three correctly rounded fp32 operations; ``mean is std is None``: ToTensor alone.  `mean` / `std` are host sequences of C numbers,
+    read at the call.  `memory_format`: ``torch.contiguous_format`` (NCHW) or ``torch.channels_last`` (dense channels-last, what
+    ``x.contiguous(memory_format=torch.channels_last)`` gives); `dtype`: ``torch.float32`` or ``torch.bfloat16`` (the fp32 value narrowed
+    once at the store, what ``x.to(torch.bfloat16)`` gives).  `out`: a buffer of that shape, layout, dtype and device to write into, else
+    ``ValueError`` (a captured graph keeps its buffer; `index` is then read on replay).  The default format on a 16-byte aligned `out`
+    (every fresh tensor) is clica_image_gather_norm's launch as before; an `out` view that is only element-aligned, which that entry
+    point refuses, is served by clica_image_gather_norm_ex's scalar instance in every format, the default one included (same bits)."""
     N, H, W, Cn = _image_table(table)
+    layout, dt = image_format_args(memory_format, dtype)
     if (mean is None) != (std is None):
         raise ValueError("mean and std must be given together")
     m = s = None
@@ -1589,13 +1609,18 @@ def image_gather_norm(table: torch.Tensor, index: torch.Tensor, mean=None, std=N
     if n == 0 or index.dim() != 1:
         raise ValueError(f"index must be a non-empty 1-D list of rows (got shape {tuple(index.shape)})")
     if out is None:
-        out = torch.empty((n, Cn, H, W), dtype=torch.float32, device=table.device)
+        out = torch.empty((n, Cn, H, W), dtype=dtype, device=table.device, memory_format=memory_format)
     else:
-        require_cuda(out, "out")
-        if tuple(out.shape) != (n, Cn, H, W) or not out.is_contiguous() or out.device != table.device:
-            raise ValueError(f"out must be a contiguous float32 tensor {(n, Cn, H, W)} on {table.device} (got {tuple(out.shape)})")
-    check(load().clica_image_gather_norm(table.data_ptr(), N, H, W, Cn, index.data_ptr(), n, m, s, out.data_ptr(), stream_ptr()),
-          "clica_image_gather_norm")
+        if (not torch.is_tensor(out) or tuple(out.shape) != (n, Cn, H, W) or out.dtype != dtype or out.device != table.device
+                or not out.is_contiguous(memory_format=memory_format)):
+            got = f"{out.dtype} {tuple(out.shape)}, strides {tuple(out.stride())}, on {out.device}" if torch.is_tensor(out) else type(out).__name__
+            raise ValueError(f"out must be a {dtype} tensor {(n, Cn, H, W)}, dense in {memory_format}, on {table.device} (got {got})")
+    if layout == 0 and dt == 0 and out.data_ptr() % 16 == 0:      # (the one alignment the first entry point accepts for every shape)
+        check(load().clica_image_gather_norm(table.data_ptr(), N, H, W, Cn, index.data_ptr(), n, m, s, out.data_ptr(), stream_ptr()),
+              "clica_image_gather_norm")
+    else:
+        check(load().clica_image_gather_norm_ex(table.data_ptr(), N, H, W, Cn, index.data_ptr(), n, m, s, out.data_ptr(), layout, dt,
+                                                stream_ptr()), "clica_image_gather_norm_ex")
     return out
 
 

@@ -13,15 +13,19 @@ sphere, von Mises-Fisher kappa from 0.01 to 1e4 (n = 1 is refused: S^0 has no ta
 """
 from __future__ import annotations
 
+import contextlib
 from abc import ABC, abstractmethod
 
 import torch
 
 from . import ops
 
-__all__ = ["Space", "NRealSpace", "NSphereSpace", "NBoxSpace", "manual_seed"]
+__all__ = ["Space", "NRealSpace", "NSphereSpace", "NBoxSpace", "manual_seed", "DeviceClock"]
 
 _state = {"seed": 0, "draw": 0}
+_clock = None      # the DeviceClock whose ``iteration()`` scope is open, else None
+
+CLOCK_STREAM_BASE = 1 << 31      # Philox stream ids of clocked draws: this + the draw's ordinal within its iteration
 
 
 def manual_seed(seed: int) -> None:
@@ -29,9 +33,68 @@ def manual_seed(seed: int) -> None:
     _state["draw"] = 0
 
 
+class DeviceClock:
+    """Draw numbering that a captured graph can replay: the iteration counter lives on the device.
+
+    The module-level generator numbers its draws with a host counter (``stream_id`` = 1, 2, ... at Philox step 0), so a recorded
+    launch would replay the same stream for ever.  Inside ``with clock.iteration():`` every draw of this module (through
+    ``LatentSpace`` / ``ProductLatentSpace`` and every kind, vMF and tensor scales included: they all reach ``_draw``) instead uses
+    Philox seed = the clock's `seed`, step = ``*clock.step`` (an ``int32[1]`` on the device, read by the kernel: ``step_dev`` of
+    ``clica_sample`` / ``clica_sample_scaled``) and stream id = ``CLOCK_STREAM_BASE`` + the ordinal of the draw within the iteration;
+    the ordinal restarts at every ``with``.  ``clock.tick()`` advances the counter by one with a stream-ordered one-thread kernel
+    (``clica_tick``): no host read, capturable.  The module-level counter is not touched inside a scope, so the draws outside are
+    what they would have been without it.
+
+    Two properties follow:
+      * an eager iteration and a replayed one at the same counter value draw the same numbers, bit for bit: host state enters only
+        through the ordinals, which the recorded iteration fixed in the same order an eager one assigns them;
+      * clocked draws never coincide with draws of the module-level generator under the same user seed: the Philox counter holds
+        (element, draw, step, stream id), clocked stream ids have bit 31 set (``CLOCK_STREAM_BASE + ordinal``, ordinal < 2^31) and
+        module-level ones are the draw numbers 1, 2, ... below 2^31 (``_draw`` refuses to count further), so the two ranges are
+        disjoint whatever the seed and the counter are.  The evaluation batches a driver draws between training steps therefore
+        never repeat a training batch.
+    """
+
+    def __init__(self, seed: int = 0, device="cuda"):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(f"DeviceClock lives on the GPU only (device={device!r})")
+        self.seed = int(seed)
+        self.device = device
+        self.step = torch.zeros(1, dtype=torch.int32, device=device)
+        self._ordinal = 0
+
+    @contextlib.contextmanager
+    def iteration(self):
+        """Scope of ONE iteration: the draws inside are clocked, their ordinals start at 0."""
+        global _clock
+        if _clock is not None:
+            raise RuntimeError("DeviceClock.iteration: a clock scope is already open (scopes do not nest)")
+        _clock, self._ordinal = self, 0
+        try:
+            yield self
+        finally:
+            _clock = None
+
+    def tick(self) -> None:
+        """``*step += 1`` on the current stream."""
+        ops.tick(self.step)
+
+    def _next(self) -> int:
+        if self._ordinal >= CLOCK_STREAM_BASE:
+            raise RuntimeError("DeviceClock: more than 2^31 draws in one iteration")
+        self._ordinal += 1
+        return CLOCK_STREAM_BASE + self._ordinal - 1
+
+
 def _draw(space, dist, n, size, device, **kw):
     if device is None or torch.device(device).type != "cuda":
         raise RuntimeError(f"cl_ica_amd.spaces samples on the GPU only (device={device!r}); there is no host fallback")
+    if _clock is not None:
+        return ops.sample(space, dist, n, size, torch.device(device), seed=_clock.seed, stream_id=_clock._next(), step_dev=_clock.step,
+                          **kw)
+    if _state["draw"] + 1 >= CLOCK_STREAM_BASE:
+        raise RuntimeError("cl_ica_amd.spaces: 2^31 draws since manual_seed (the stream ids above belong to DeviceClock)")
     _state["draw"] += 1
     return ops.sample(space, dist, n, size, torch.device(device), seed=_state["seed"], stream_id=_state["draw"], **kw)
 

@@ -21,11 +21,11 @@ from typing import Callable, Optional
 import torch
 from torch import nn
 
-from . import encoders, layers, lazy, losses, ops
+from . import _lib, encoders, layers, lazy, losses, ops, optim, spaces
 from .encoders import _MLPStackFn
 
 __all__ = ["setup_f", "make_unsupervised_loss", "train_step", "HipLinear", "unpack_item_list", "make_supervised_loss",
-           "train_step_supervised"]
+           "train_step_supervised", "batch_format", "clocked_iteration", "capture_iteration", "CapturedIteration"]
 
 
 class HipLinear(nn.Linear):
@@ -183,6 +183,7 @@ def _mse_workspace(M: int, n: int, device) -> torch.Tensor:
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError(f"mse loss: no workspace for shape ({M}, {n}) yet -- run the step once eagerly before capturing it")
         ws = _MSE_WS[key] = ops.mse_loss_workspace(M, n, device)
+    _lib.note_graph_use(ws)
     return ws
 
 
@@ -230,3 +231,152 @@ def train_step_supervised(data, loss, optimizer, f, sync: bool = True, amp=None)
     if not sync:
         return total_loss_value
     return total_loss_value.item()
+
+
+# ------------------------------------------------------------------------------------------------ the iteration as one HIP graph
+def batch_format(f, amp=None):
+    """``(memory_format, dtype)`` of the image batch the model takes without a copy in front of it: channels-last bf16 under
+    ``amp="bf16"`` (what ``conv1`` under autocast computes on), else float32 in the memory format of the model's first 4-D parameter."""
+    if amp == "bf16":
+        return torch.channels_last, torch.bfloat16
+    if amp is not None:
+        raise ValueError(f"amp={amp!r} (one of {AMP_MODES})")
+    for p in f.parameters():
+        if p.dim() == 4:
+            if p.is_contiguous(memory_format=torch.channels_last) and not p.is_contiguous():
+                return torch.channels_last, torch.float32
+            break
+    return torch.contiguous_format, torch.float32
+
+
+def clocked_iteration(dataset, loss, optimizer, f, batch_size: int, clock, *, supervised: bool = False, amp=None, latents=None,
+                      images=None):
+    """ONE training iteration with its batch drawn under `clock` (``spaces.DeviceClock``): the clocked pair draw, ``snap``, one gather of
+    both views, ``train_step`` (``train_step_supervised`` when `supervised`) without host reads, ``clock.tick()``.  `latents`
+    ``(z, z~)`` / `images` ``(2 B, C, H, W)``: buffers the batch is written into (the captured iteration's static ones); ``None``: fresh
+    tensors in ``batch_format(f, amp)``.  Returns ``((total, per_item, parts), (z, z~), images)``; the supervised step has no per-item
+    vector and no parts (``None``).  Every launch is stream-ordered and reads its counters on the device: the call can be captured
+    once its workspaces exist."""
+    B = int(batch_size)
+    memory_format, dtype = batch_format(f, amp)
+    with clock.iteration():
+        index_z, index_zt, z, zt = dataset.pairs.sample(B)
+    if latents is not None:
+        latents[0].copy_(z); latents[1].copy_(zt)
+        z, zt = latents
+    x = dataset.images.gather(torch.cat([index_z, index_zt]), dataset.normalize, images, memory_format=memory_format, dtype=dtype)
+    data = ((z, zt), (x[:B], x[B:]))
+    if supervised:
+        out = (train_step_supervised(data, loss, optimizer, f, sync=False, amp=amp), None, None)
+    else:
+        out = tuple(train_step(data, loss, optimizer, f, sync=False, amp=amp))
+        if len(out) == 2:                  # the combined objective returns (total, parts)
+            out = (out[0], None, out[1])
+    clock.tick()
+    return out, (z, zt), x
+
+
+def _scale_layers(module):
+    """The ``RescaleLayer`` / ``SoftclipLayer`` instances under `module`, those held in the closure of a ``layers.Lambda`` (the
+    combined rescaling of ``make_rescaling``) included."""
+    for m in module.modules():
+        if isinstance(m, (layers.RescaleLayer, layers.SoftclipLayer)):
+            yield m
+        elif isinstance(m, layers.Lambda):
+            for cell in getattr(m.f, "__closure__", None) or ():
+                if isinstance(cell.cell_contents, nn.Module):
+                    yield from _scale_layers(cell.cell_contents)
+
+
+def _scales_to_device(f, device) -> None:
+    """A fixed radius / bound is a plain host tensor, neither parameter nor buffer (as in the reference), and its layer copies it to the
+    device in every forward: a host copy that cannot be recorded.  Put those tensors (and a learnable one held only in a closure) on
+    `device` once, ahead of the capture; the layers' ``.to(x.device)`` is then the tensor itself.  State dicts do not hold them."""
+    for m in _scale_layers(f):
+        name = "r" if isinstance(m, layers.RescaleLayer) else "max_abs_bound"
+        t = getattr(m, name)
+        if t.device != device:
+            if isinstance(t, nn.Parameter):
+                t.data = t.data.to(device)
+            else:
+                setattr(m, name, t.to(device))
+
+
+class CapturedIteration:
+    """What ``capture_iteration`` returns: ``step()`` replays the graph (one launch) and returns ``(total, per_item, parts)``, device
+    tensors owned by the graph and rewritten by every replay.  ``latents`` ``(z, z~)`` and ``images`` ``(2 B, C, H, W)`` are the static
+    batch of the last replay, ``graph`` the ``torch.cuda.CUDAGraph``, ``clock`` the device clock, ``owned`` the buffers of the package's
+    caches that the recorded launches use (kept alive and kept from other owners through ``_lib.pin`` while this object lives)."""
+
+    def __init__(self, graph, result, latents, images, clock, owned):
+        self.graph, self.result, self.latents, self.images, self.clock, self.owned = graph, result, latents, images, clock, owned
+        self.replays = 0
+
+    def __call__(self):
+        self.graph.replay()
+        self.replays += 1
+        return self.result
+
+
+def capture_iteration(dataset, loss, optimizer, f, batch_size: int, *, supervised: bool = False, amp=None, warmup: int = 3, clock=None,
+                      on_warmup=None):
+    """The whole 3DIdent training iteration -- clocked pair draw, ``snap``, image gather, encoder passes, loss, ``backward()``,
+    ``all_reduce_grads`` if present, ``optimizer.step()``, ``clock.tick()`` (``clocked_iteration``) -- recorded into ONE HIP graph on
+    static buffers; returns ``step`` (``CapturedIteration``).
+
+    `warmup` (at least 1) ordinary eager iterations run first on the capture stream, inside the clock scope, and they TRAIN: the MIOpen
+    find step, the growth of the workspaces and the allocations of the graph's pool happen there (the fused units of ``resnet`` raise
+    when they are captured without one).  ``on_warmup(result)`` is called after each with its ``(total, per_item, parts)``.  A run of
+    ``warmup`` eager iterations followed by replays visits the batch sequence of an all-eager run of ``clocked_iteration`` under the
+    same clock: iteration k draws with the counter at k either way.  Fixed radii / bounds of the rescaling layers (plain host
+    tensors) are moved to the device first (``_scales_to_device``).  `clock`: default ``spaces.DeviceClock`` seeded with the module-level
+    generator's seed.  Capture is on one stream, no forked branches.
+
+    The optimizer must be ``optim.Adam`` or ``optim.SGD`` (flat arenas, step counter on the device); a dataset of ``dummy_images`` has
+    no image batch to gather and is refused (``--dummy-mixing`` and ``--identity-mixing-and-solution`` of the driver, whose steps run
+    eagerly), and so is a model without parameters (``--identity-solution``).  Evaluation, other batch sizes and other encoders may
+    run eagerly between replays: the cache-held buffers of the recorded launches are owned by the returned object."""
+    if not isinstance(optimizer, (optim.Adam, optim.SGD)):
+        raise TypeError(f"capture_iteration: the optimizer must be cl_ica_amd.optim.Adam or optim.SGD (flat arenas, step counter on the "
+                        f"device), got {type(optimizer).__name__}")
+    if getattr(dataset, "dummy_images", False) or getattr(dataset, "images", None) is None:
+        raise ValueError("capture_iteration: the dataset has no images (dummy_images): there is no image batch to capture")
+    if not any(p.requires_grad for p in f.parameters()):
+        raise ValueError("capture_iteration: the model has no trainable parameters (identity solution): there is nothing to capture")
+    if optimizer.world > 1:
+        raise RuntimeError("capture_iteration: the data-parallel step (collectives issued from Python) is not captured")
+    if _lib._CAPTURE_NOTES is not None:
+        raise RuntimeError("capture_iteration: another capture is in progress")
+    device = dataset.device
+    B = int(batch_size)
+    if clock is None:
+        clock = spaces.DeviceClock(spaces._state["seed"], device)
+    memory_format, dtype = batch_format(f, amp)
+    _scales_to_device(f, device)
+    _N, H, W, Cn = dataset.images.shape
+    images = torch.empty((2 * B, Cn, H, W), dtype=dtype, device=device, memory_format=memory_format)
+    d = dataset.latents.shape[1]
+    latents = (torch.empty((B, d), dtype=torch.float32, device=device), torch.empty((B, d), dtype=torch.float32, device=device))
+    kw = dict(supervised=supervised, amp=amp, latents=latents, images=images)
+
+    side = torch.cuda.Stream(device=device)
+    side.wait_stream(torch.cuda.current_stream(device))
+    with torch.cuda.stream(side):
+        for _ in range(max(1, int(warmup))):
+            out, _z, _x = clocked_iteration(dataset, loss, optimizer, f, B, clock, **kw)
+            if on_warmup is not None:
+                on_warmup(out)
+    torch.cuda.current_stream(device).wait_stream(side)
+    torch.cuda.synchronize(device)
+
+    graph = torch.cuda.CUDAGraph()
+    notes = _lib._CAPTURE_NOTES = []
+    try:
+        with torch.cuda.graph(graph, stream=side):
+            result, _z, _x = clocked_iteration(dataset, loss, optimizer, f, B, clock, **kw)
+    finally:
+        _lib._CAPTURE_NOTES = None
+    owned = list({id(t): t for t in notes}.values())
+    step = CapturedIteration(graph, result, latents, images, clock, owned)
+    _lib.pin(step, owned)
+    return step

@@ -19,7 +19,12 @@ Where it differs from the reference (INTEGRATION.md lists the same):
     here takes both shapes and prints ``sigma(loss): nan`` when there is no per-item vector;
   * ``--encoder`` also accepts ``rn152`` (the reference's choices say ``rn151``, its table ``rn152``);
   * ``--no-cuda`` exits: there is no CPU path; ``--workers`` / ``--faiss-omp-threads`` are accepted and unused;
-  * extra flags: ``--seed`` (numpy / random / torch / the device samplers), ``--image-cache FILE`` (the decoded image folder, written once).
+  * extra flags: ``--seed`` (numpy / random / torch / the device samplers), ``--image-cache FILE`` (the decoded image folder, written once);
+  * ``--graph`` (default off) replays the whole training iteration -- batch draw, snap, image gather, encoder, loss, backward, optimizer --
+    as ONE HIP graph (``threedident.capture_iteration``; the first iteration runs eagerly and trains).  The training batches are then
+    drawn under a device clock (``spaces.DeviceClock``), so the batch sequence differs from a run without the flag under the same
+    ``--seed``; the evaluation batches still come from the module-level generator.  Log lines, schedule and model files are the same.
+    Refused with ``--dummy-mixing`` / ``--identity-solution`` / ``--identity-mixing-and-solution`` (no image batch or nothing to train).
 One process, one GPU.
 """
 from __future__ import annotations
@@ -85,11 +90,15 @@ _EXTRA_ARGS = [
     ("--amp", dict(default="off", choices=("off", "bf16"),
                    help="bf16: the backbone in bf16 mixed precision (autocast convolutions, channels-last bf16 HIP units between them); "
                         "head, loss, optimizer and model files stay fp32.")),
+    ("--graph", dict(default="off", choices=("off", "on"), nargs="?", const="on",
+                     help="on (or the bare flag): the training iteration, batch draw included, is recorded once and replayed as one HIP "
+                          "graph; the training batches are then drawn under a device clock, so the batch sequence differs from a run "
+                          "without the flag under the same --seed.")),
 ]
 # The flags of _EXTRA_ARGS that say HOW the run computes, not what it computes.  They are taken off the command line ahead of the
 # table's parser: build_parser() stays the reference's surface plus --seed and --image-cache, the set tests/test_train_3dident_host.py
 # pins.
-_RUN_ARGS = ("--amp",)
+_RUN_ARGS = ("--amp", "--graph")
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -133,6 +142,9 @@ def parse_args(argv=None):
     if args.amp != "off" and (args.dummy_mixing or args.identity_solution or args.identity_mixing_and_solution):
         raise AssertionError(f"--amp {args.amp} is the backbone's mixed precision: --dummy-mixing / --identity-solution / "
                              "--identity-mixing-and-solution have no backbone")
+    if args.graph != "off" and (args.dummy_mixing or args.identity_solution or args.identity_mixing_and_solution):
+        raise AssertionError("--graph captures the iteration on image batches: --dummy-mixing (latents through an MLP), --identity-solution "
+                             "and --identity-mixing-and-solution (nothing to train) have nothing to capture and run without it")
     return args
 
 
@@ -140,6 +152,30 @@ def _amp(args):
     """What the steps and the evaluation take as ``amp``: None for ``--amp off`` (and for argument objects from before the flag)."""
     amp = getattr(args, "amp", "off")
     return None if amp == "off" else amp
+
+
+def _graph(args) -> bool:
+    """``--graph`` (False for argument objects from before the flag)."""
+    return getattr(args, "graph", "off") not in ("off", False, None)
+
+
+class _GraphedSteps:
+    """The loop's training step under ``--graph``: the first call runs one eager clocked iteration (it trains; the find step and the
+    workspaces happen there) and records the graph, every later call is one replay.  Returns ``(total, per_item, parts)``; ``total`` is a
+    copy, because the graph rewrites its own on the next replay and the loop keeps the values on the device until the next log step."""
+
+    def __init__(self, dataset, loss, optimizer, f, batch_size, supervised, amp):
+        self.args = (dataset, loss, optimizer, f, batch_size)
+        self.kw = dict(supervised=supervised, amp=amp, warmup=1)
+        self.step = None
+
+    def __call__(self):
+        if self.step is None:
+            first = []
+            self.step = threedident.capture_iteration(*self.args, on_warmup=first.append, **self.kw)
+            return first[0]
+        total, per_item, parts = self.step()
+        return total.detach().clone(), per_item, parts
 
 
 def _amp_batch(x, amp):
@@ -354,21 +390,26 @@ def train_unsupervised(args, train_loader, f, n_non_angular_latents, g=None):
     identity_scale = 1.0
     last_save_at_step = 0
     scores = None
+    graphed = _GraphedSteps(train_loader.dataset, loss, optimizer, f, args.batch_size, False, amp) if _graph(args) else None
     for global_step in range(n_steps):
-        data = next(train_iterator)
-        (z1, z2_con_z1), (x1, x2_con_x1) = data
-        if args.dummy_mixing:
-            with torch.no_grad():
-                data = ((z1, z2_con_z1), (g(z1), g(z2_con_z1)))
-        if args.identity_mixing_and_solution:      # h = f o g is the identity: the objective on the latents themselves, nothing to train
-            z1_rec = z1 * identity_scale
-            total, per_item, _parts = loss(None, None, None, z1_rec, z2_con_z1 * identity_scale, torch.roll(z1_rec, 1, 0))
+        if graphed is not None:      # the batch is drawn inside the iteration, under the device clock
+            total, per_item, _parts = graphed()
+            pending.append(total)
         else:
-            if amp is not None:
-                data = ((z1, z2_con_z1), (_amp_batch(data[1][0], amp), _amp_batch(data[1][1], amp)))
-            total, per_item, _parts = threedident.train_step(data, loss, optimizer, f, sync=False, amp=amp)
-        pending.append(total)
-        del data, x1, x2_con_x1
+            data = next(train_iterator)
+            (z1, z2_con_z1), (x1, x2_con_x1) = data
+            if args.dummy_mixing:
+                with torch.no_grad():
+                    data = ((z1, z2_con_z1), (g(z1), g(z2_con_z1)))
+            if args.identity_mixing_and_solution:      # h = f o g is the identity: the objective on the latents themselves, nothing to train
+                z1_rec = z1 * identity_scale
+                total, per_item, _parts = loss(None, None, None, z1_rec, z2_con_z1 * identity_scale, torch.roll(z1_rec, 1, 0))
+            else:
+                if amp is not None:
+                    data = ((z1, z2_con_z1), (_amp_batch(data[1][0], amp), _amp_batch(data[1][1], amp)))
+                total, per_item, _parts = threedident.train_step(data, loss, optimizer, f, sync=False, amp=amp)
+            pending.append(total)
+            del data, x1, x2_con_x1
         log = is_log_step(global_step, n_log_steps, n_steps)
         if log:
             scores = evaluate(args, f, train_iterator, True, g=g, amp=amp)
@@ -412,6 +453,7 @@ def train_supervised(args, train_loader, f, g=None):
     train_iterator = _infinite(train_loader)
     last_save_at_step = 0
     scores = None
+    graphed = _GraphedSteps(train_loader.dataset, loss, optimizer, f, args.batch_size, True, amp) if _graph(args) else None
     for global_step in range(n_steps):
         log = is_log_step(global_step, n_log_steps, n_steps)
         if log:
@@ -421,8 +463,10 @@ def train_supervised(args, train_loader, f, g=None):
             linear_score = permutation_score = np.inf
         linear_scores.append(linear_score)
         permutation_scores.append(permutation_score)
-        data = next(train_iterator)
-        if not args.identity_solution:
+        data = next(train_iterator) if graphed is None else None
+        if graphed is not None:
+            pending.append(graphed()[0])
+        elif not args.identity_solution:
             if args.dummy_mixing:
                 (z1, z2), _x = data
                 with torch.no_grad():

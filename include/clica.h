@@ -1030,6 +1030,18 @@ int clica_kitti_sample_pairs(const uint8_t* frames, int64_t frame_elems, int64_t
  * ---------------------------------------------------------------------------------- */
 int clica_image_gather_norm(const uint8_t* table, int64_t n_images, int32_t H, int32_t W, int32_t C, const int64_t* index,
                             int64_t n_index, const float* mean, const float* std, float* out, clica_stream_t stream);
+/* The same values in the layout and element type the consumer takes.  layout NCHW: out[n_index][C][H][W]; NHWC: out[n_index][H][W][C]
+ * (a dense channels-last batch: the table row's own element order).  dtype F32: the value above; BF16 (uint16_t bits): that fp32 value
+ * narrowed once at the store, round to nearest even, NaN -> 0x7fc0 (what Tensor.to(torch.bfloat16) gives).  out must be aligned to its
+ * element.  Wide path, chosen here from the sizes and BOTH pointers (table 4-byte, out 4-element aligned), never assumed: NCHW with C == 3
+ * and H W % 4 == 0 as above (8-byte stores for bf16); NHWC with H W C % 4 == 0: one 32-bit load, four conversions and one 16-byte (bf16:
+ * 8-byte) store per thread, channel of element e = e % C.  Every other case: one element (NCHW: pixel) per thread, same bits.
+ * clica_image_gather_norm stays what it was (NCHW fp32, alignment required). */
+enum clica_image_layout { CLICA_IMAGE_NCHW = 0, CLICA_IMAGE_NHWC = 1 };
+enum clica_image_dtype { CLICA_IMAGE_F32 = 0, CLICA_IMAGE_BF16 = 1 };
+int clica_image_gather_norm_ex(const uint8_t* table, int64_t n_images, int32_t H, int32_t W, int32_t C, const int64_t* index,
+                               int64_t n_index, const float* mean, const float* std, void* out, int32_t layout, int32_t dtype,
+                               clica_stream_t stream);
 int clica_image_channel_stats(const uint8_t* table, int64_t n_images, int32_t H, int32_t W, int32_t C, uint64_t* sums,
                               clica_stream_t stream);
 

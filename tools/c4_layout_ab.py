@@ -7,6 +7,10 @@
     (d) nhwc-hip-stem  as (c) with CLICA_RESNET_NHWC_STEM=hip: the stem's bn1 + relu + maxpool as the fused unit of csrc/bn2d_nhwc.hip
     (e) nhwc-torch-bf16     as (b) with the encoder passes under torch.autocast(bfloat16): what bf16 mixed precision was before BF16_MODE
     (f) nhwc-hip-stem-bf16  as (d) under the same autocast with CLICA_RESNET_BF16=hip: the bf16 instances of csrc/bn2d_nhwc.hip
+    (g) <leg>-clocked       the leg's step as threedident.clocked_iteration: the batch is drawn under a device clock, snapped to a
+                            synthetic grid of 4096 latents and gathered from a 4096 x 64 x 64 x 3 uint8 table in the model's format
+                            inside every iteration (legs a - f step on two fixed tensors and draw nothing), launched from Python
+    (h) <leg>-graph         the same iteration recorded once and replayed as ONE HIP graph (threedident.capture_iteration)
 
   python tools/c4_layout_ab.py                      a throw-away run of every leg (MIOpen's find step), then two rounds alternating the
                                                     legs; each figure the median of three 20-step windows after 6 warm-up steps
@@ -34,6 +38,10 @@ LEGS = {"nchw": ("contiguous", "torch", "torch"), "nhwc-torch": ("channels_last"
         "nhwc-torch-bf16": ("channels_last", "torch", "torch"), "nhwc-hip-stem-bf16": ("channels_last", "hip", "hip")}
 # leg -> (BF16_MODE, train_step's amp); every other leg: ("torch", None)
 BF16_LEGS = {"nhwc-torch-bf16": ("torch", "bf16"), "nhwc-hip-stem-bf16": ("hip", "bf16")}
+# the legs whose iteration draws its own batch: eager under the device clock, and the captured graph of that
+BATCH_LEGS = {leg + sfx: (leg, sfx[1:]) for leg in ("nchw", "nhwc-hip-stem", "nhwc-hip-stem-bf16") for sfx in ("-clocked", "-graph")}
+ALL_LEGS = list(LEGS) + list(BATCH_LEGS)
+TABLE_IMAGES = 4096
 # ResNet-18's units at N = 1024 on 64 x 64 images: (name, N, C, H, W, units with / without a residual per view)
 UNIT_SHAPES = [("stem", 1024, 64, 32, 32), ("layer 1", 1024, 64, 16, 16), ("layer 2", 1024, 128, 8, 8), ("layer 3", 1024, 256, 4, 4),
                ("layer 4", 1024, 512, 2, 2)]
@@ -52,6 +60,7 @@ def make_leg(leg):
     import torch
     from cl_ica_amd import resnet, threedident as T
     from cl_ica_amd.optim import Adam
+    leg, batches = BATCH_LEGS.get(leg, (leg, None))
     fmt_name, nhwc_mode, stem_mode = LEGS[leg]
     bf16_mode, amp = BF16_LEGS.get(leg, ("torch", None))
     fmt = getattr(torch, fmt_name + "_format" if fmt_name == "contiguous" else fmt_name)
@@ -67,6 +76,8 @@ def make_leg(leg):
         f[0].register_forward_hook(lambda mod, inp, out: out.float())
     loss = T.make_unsupervised_loss(a, 3)
     opt = Adam(f.parameters(), lr=1e-4)
+    if batches is not None:
+        return make_batch_leg(batches, f, loss, opt, amp, (nhwc_mode, stem_mode, bf16_mode))
     x1 = torch.randn(1024, 3, 64, 64, device=dev)
     x2 = (x1 + 0.1 * torch.randn_like(x1)).contiguous(memory_format=fmt)
     x1 = x1.contiguous(memory_format=fmt)
@@ -79,10 +90,44 @@ def make_leg(leg):
     return step
 
 
+def make_batch_leg(how, f, loss, opt, amp, modes):
+    """The leg's step with the batch inside: `how` = "clocked" (eager) or "graph" (one replay)."""
+    import tempfile
+    import numpy as np
+    import torch
+    from cl_ica_amd import latent_spaces, resnet, spaces, threedident as T
+    from cl_ica_amd.datasets import ThreeDIdentDataset
+    rng = np.random.default_rng(0)
+    ls = latent_spaces.LatentSpace(spaces.NBoxSpace(3), lambda s, size, device="cuda": s.uniform(size, device=device),
+                                   lambda s, z, size, device="cuda": s.normal(z, 0.1, size, device=device))
+    with tempfile.TemporaryDirectory() as root:
+        np.save(os.path.join(root, "raw_latents.npy"), rng.uniform(-1, 1, size=(TABLE_IMAGES, 3)).astype(np.float32))
+        images = torch.randint(0, 256, (TABLE_IMAGES, 64, 64, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(0))
+        ds = ThreeDIdentDataset(root, ls, images=images, normalize=([0.3292, 0.3278, 0.3215], [0.0778, 0.0776, 0.0771]))
+    clock = spaces.DeviceClock(0, "cuda")
+
+    def set_modes():
+        resnet.NHWC_MODE, resnet.NHWC_STEM_MODE, resnet.BF16_MODE = modes
+
+    if how == "clocked":
+        def step():
+            set_modes()
+            return T.clocked_iteration(ds, loss, opt, f, 1024, clock, amp=amp)[0][0]
+        return step
+    set_modes()
+    first = []
+    captured = T.capture_iteration(ds, loss, opt, f, 1024, amp=amp, warmup=2, clock=clock, on_warmup=lambda r: first.append(r[0].clone()))
+
+    def step():                                       # every call is one replay: the two eager warm-up iterations ran above
+        return captured()[0]
+    step.captured, step.first_loss = captured, first[0]
+    return step
+
+
 def run_leg(leg, steps, warmup, windows):
     import torch
     step = make_leg(leg)
-    first = None
+    first = getattr(step, "first_loss", None)         # (a -graph leg ran its first iteration while it was being recorded)
     for _ in range(warmup):
         last = step()
         first = last if first is None else first
@@ -99,7 +144,7 @@ def run_leg(leg, steps, warmup, windows):
     el = statistics.median(ws)
     res = {"leg": leg, "steps_per_s": round(steps / el, 2), "ms_per_step": round(1e3 * el / steps, 2), "final_loss": round(float(last.item()), 5),
            "windows_s": [round(w, 4) for w in ws]}
-    if leg in BF16_LEGS and first is not None:
+    if (leg in BF16_LEGS or leg in BATCH_LEGS) and first is not None:
         res["first_loss"] = round(float(first.item()), 5)
     del step
     torch.cuda.empty_cache()
@@ -305,7 +350,7 @@ def summarise(path, out, top=45):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--leg", choices=sorted(LEGS), help="run this leg alone (for a profiler)")
+    ap.add_argument("--leg", choices=sorted(ALL_LEGS), help="run this leg alone (for a profiler)")
     ap.add_argument("--legs", default=None, help="comma-separated legs of the alternating run (default: all)")
     ap.add_argument("--units", action="store_true")
     ap.add_argument("--summarise", metavar="KERNEL_TRACE_CSV")
@@ -325,9 +370,9 @@ def main():
         return bf16_units(args.out)
     if args.leg:
         return emit(args.out, dict(run_leg(args.leg, args.steps or 30, args.warmup, 1), run="alone"))
-    legs = args.legs.split(",") if args.legs else list(LEGS)
-    if any(leg not in LEGS for leg in legs):
-        raise SystemExit(f"--legs {args.legs!r}: legs are {sorted(LEGS)}")
+    legs = args.legs.split(",") if args.legs else list(LEGS)      # (the batch legs run when named)
+    if any(leg not in ALL_LEGS for leg in legs):
+        raise SystemExit(f"--legs {args.legs!r}: legs are {sorted(ALL_LEGS)}")
     for leg in legs:                                   # MIOpen's find step of every leg, outside every window
         emit(args.out, dict(run_leg(leg, 4, 2, 1), run="throw-away"))
     for rnd in range(1, args.rounds + 1):
